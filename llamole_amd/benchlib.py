@@ -6,7 +6,8 @@ only code of this repository besides tests/ and __graft_entry__.smoke() allowed 
   * algorithmic bytes / flops of a GraphDiT reverse step (``dit_step_bytes`` / ``dit_step_flops``; DESIGN.md section 4);
   * kernel timing: the dominant hand-written kernel of each workload with HIP events on the stream it runs on (``time_dominant_kernel``,
     ``time_template_head``), the GraphDiT fc1 GEMM in situ (event bracket, empty-pair calibration, marginal cost), ``roofline_object``;
-  * the retro (BASELINE configs[2]) and sft (configs[4]) workloads as ``run_retro`` / ``run_sft`` (the CPU baseline is handed in by bench.py).
+  * the retro (BASELINE configs[2]) and sft (configs[4]) workloads as ``run_retro`` / ``run_sft`` (the CPU baseline is handed in by bench.py;
+    it, the template-head roofline and the graph-side timing run only under ``--full``).
 """
 import json
 import os
@@ -83,6 +84,17 @@ def build_model(args, device):
         for p in m.parameters():
             p.data = p.data.to(dtype)
     return m, cfg, meta, sd
+
+
+def pack_molecules(mols, max_nodes: int) -> dict:
+    """Integer graphs as fixed-shape arrays: atom types [M, N], edge types [M, N, N] (-1 past a graph's atoms) and atom counts [M]."""
+    atoms = np.full((len(mols), max_nodes), -1, np.float32)
+    edges = np.full((len(mols), max_nodes, max_nodes), -1, np.float32)
+    n_atoms = np.zeros(len(mols), np.float32)
+    for i, (a, e) in enumerate(mols):
+        n = int(a.shape[0])
+        atoms[i, :n], edges[i, :n, :n], n_atoms[i] = a.numpy(), e.numpy(), n
+    return {"atom_types": atoms, "edge_types": edges, "n_atoms": n_atoms}
 
 
 def usable_cores() -> int:
@@ -406,8 +418,9 @@ def value_forward_mfma(llm, tokens: int, seconds: float):
             "kernel": "hipBLASLt MT256x256x64 GEMMs under the stock HF prefill (77 % of the forward, profiles/r3_value_forward_kernel_stats.csv)"}
 
 
-def run_retro(args, ctx, cpu_baseline_fn=None):
-    """BASELINE.json configs[2]: design + lock-step A* retrosynthesis for `targets` prompts per GPU (llamole_amd/workloads.py)."""
+def run_retro(args, ctx, cpu_baseline_fn=None, outputs=None):
+    """BASELINE.json configs[2]: design + lock-step A* retrosynthesis for `targets` prompts per GPU (llamole_amd/workloads.py).
+    `outputs` (a dict, on rank 0) receives what the last timed step returned: the route records and rank 0's designed molecules."""
     from llamole_amd.workloads import build_retro_step
     m, cfg, meta, sd = build_model(args, ctx.device)
     step_fn, info, orch, llm, sd_pred = build_retro_step(args, m, ctx.device, ctx.rank, ctx.world)
@@ -422,6 +435,7 @@ def run_retro(args, ctx, cpu_baseline_fn=None):
         _maybe_fail(ctx.rank, i)
         mols, rec = step_fn(args.warmup + i)
         recs.append(rec)
+        last_mols = mols
         design_s += info["timing_breakdown"]["design_s"]
         retro_s += info["timing_breakdown"]["retro_s"]
         value_s += info["timing_breakdown"]["value_forward_s"]
@@ -447,9 +461,15 @@ def run_retro(args, ctx, cpu_baseline_fn=None):
     T = args.total_targets if strong else args.targets
     if strong:
         gathered = recs[-1]                  # every rank holds all routes already (replicated A*)
-    roof = time_template_head(args, T if not strong else max(3, T // ctx.world))
-    roof["note"] = ("dominant HAND-WRITTEN kernel of the workload; the step's dominant kernel overall is hipBLASLt's MT256x256x64 GEMM under the stock "
-                    "HF forward of the A* value estimates (78 % of that forward, profiles/r3_value_forward_kernel_stats.csv; see value_forward_share_of_step)")
+    if outputs is not None:
+        outputs["route_records"] = gathered.numpy()          # per search: route found, route length, product of the reactions' exp(-cost)
+        outputs.update({"design_" + k: v for k, v in pack_molecules(last_mols, args.nodes).items()})
+    roof = None
+    if args.full:
+        roof = time_template_head(args, T if not strong else max(3, T // ctx.world))
+        roof["note"] = ("dominant HAND-WRITTEN kernel of the workload; the step's dominant kernel overall is hipBLASLt's MT256x256x64 GEMM under the "
+                        "stock HF forward of the A* value estimates (78 % of that forward, profiles/r3_value_forward_kernel_stats.csv; see "
+                        "value_forward_share_of_step)")
     out = {"metric": "retrosynthesis-planned molecules/sec (design + A* search, depth <= %d)" % args.iterations,
            "value": (T if strong else ctx.world * T) * args.steps / dt, "unit": "molecules/s", "n_gpus": ctx.n_ranks, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "bf16",
@@ -473,9 +493,10 @@ def run_retro(args, ctx, cpu_baseline_fn=None):
                                  "reference runs one forward per node" % orch.value_batch,
            "routes_found": int(gathered[:, 0].sum().item()),
            "route_lengths": sorted(int(v) for v in gathered[gathered[:, 0] > 0, 1].tolist()),
-           "searches_without_route": int((gathered[:, 0] == 0).sum().item()),
-           "roofline": roof}
-    if not args.no_cpu_baseline and ctx.world == 1:
+           "searches_without_route": int((gathered[:, 0] == 0).sum().item())}
+    if roof is not None:
+        out["roofline"] = roof
+    if args.full and not args.no_cpu_baseline and ctx.world == 1:
         log("cpu baseline ...")
         if cpu_baseline_fn is not None:
             out["cpu_baseline"] = cpu_baseline_fn(args, llm, sd_pred, usable_cores(), n_val / max(1, n_exp))
@@ -498,8 +519,9 @@ def sft_llm_mfma(model, rows: int, seq: int, step_s: float):
             "kernel": "hipBLASLt GEMMs + flash attention under the stock HF forward / backward (profiles/r3_sft_kernel_stats.csv)"}
 
 
-def run_sft(args, ctx, cpu_baseline_fn=None):
-    """BASELINE.json configs[4]: one SFT optimizer step per bench step, data-parallel over the ranks (llamole_amd/workloads.py)."""
+def run_sft(args, ctx, cpu_baseline_fn=None, outputs=None):
+    """BASELINE.json configs[4]: one SFT optimizer step per bench step, data-parallel over the ranks (llamole_amd/workloads.py).
+    `outputs` (a dict, on rank 0) receives the losses of the last timed step."""
     from llamole_amd.workloads import build_sft_step
     step_fn, info, model, sd_pred, batch = build_sft_step(args, ctx.device, ctx.rank)
     log("sft workload built")
@@ -516,11 +538,8 @@ def run_sft(args, ctx, cpu_baseline_fn=None):
         return None
     B, S = args.sft_batch, args.sft_seq
     n_retro = int(batch["retro_product_graphs"].num_graphs)
-    graph_ms = step_fn.graph_side_ms()
-    roof = time_template_head(args, n_retro)
-    roof["kernel"] += "; the reverse sweep streams the same 740 MB once more (dlogits x W, 16-way split-K)"
-    roof["note"] = ("dominant HAND-WRITTEN kernel of the workload (graph side of the loss, graph_side_share of the step); the step itself is the stock HF "
-                    "forward / backward of the LLM under PyTorch autograd (hipBLASLt GEMMs)")
+    if outputs is not None:
+        outputs.update({k: np.array([logd[k]], np.float64) for k in ("loss", "lm_loss", "retro_loss") if logd.get(k) is not None})
     out = {"metric": "SFT samples/sec (LM loss + retro cross-entropy, LoRA)", "value": ctx.world * B * args.steps / dt, "unit": "samples/s",
            "n_gpus": ctx.n_ranks, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
@@ -529,12 +548,18 @@ def run_sft(args, ctx, cpu_baseline_fn=None):
                       "global_batch": ctx.world * B, "seq_len": S, "parallelism": "dp%d" % ctx.world,
                       "gradient_exchange": "one direct all-reduce per 64 MB bucket of the trainable set (llamole_amd.distributed.allreduce_gradients)",
                       **{k: v for k, v in info.items() if k != "last_log"}},
-           "tokens_per_s": ctx.world * B * S * args.steps / dt, "graph_side_ms": graph_ms, "graph_side_share": graph_ms / (1e3 * dt / args.steps),
+           "tokens_per_s": ctx.world * B * S * args.steps / dt,
            "loss": logd["loss"], "lm_loss": logd.get("lm_loss"), "retro_loss": logd.get("retro_loss"),
            "max_memory_gb": torch.cuda.max_memory_allocated() / 2 ** 30,
-           "llm_mfma": sft_llm_mfma(model, B, S, dt / args.steps),
-           "roofline": roof}
-    if not args.no_cpu_baseline and ctx.world == 1:
+           "llm_mfma": sft_llm_mfma(model, B, S, dt / args.steps)}
+    if args.full:
+        graph_ms = step_fn.graph_side_ms()
+        roof = time_template_head(args, n_retro)
+        roof["kernel"] += "; the reverse sweep streams the same 740 MB once more (dlogits x W, 16-way split-K)"
+        roof["note"] = ("dominant HAND-WRITTEN kernel of the workload (graph side of the loss, graph_side_share of the step); the step itself is the stock "
+                        "HF forward / backward of the LLM under PyTorch autograd (hipBLASLt GEMMs)")
+        out.update(graph_side_ms=graph_ms, graph_side_share=graph_ms / (1e3 * dt / args.steps), roofline=roof)
+    if args.full and not args.no_cpu_baseline and ctx.world == 1:
         log("cpu baseline ...")
         del model
         torch.cuda.empty_cache()

@@ -136,7 +136,8 @@ def _decode_label(mode: str, fused: dict) -> str:
 
 
 def build_e2e_step(args, graph_decoder, device, props, rank: int):
-    """Returns (step_fn, info).  step_fn(i) -> list of integer molecule graphs for the rank's batch."""
+    """Returns (step_fn, info).  step_fn(i) -> list of integer molecule graphs for the rank's batch; step_fn.last_design holds the
+    analysis tokens and the GraphDiT condition of the latest call."""
     llm = build_llm(args.llm, device)
     orch, tok = build_orchestrator(llm, graph_decoder, device)
     n_accel = 0
@@ -200,6 +201,7 @@ def build_e2e_step(args, graph_decoder, device, props, rank: int):
         torch.manual_seed(1000 * rank + i)
         t0 = time.perf_counter()
         analysis, design_ids, cond = orch.design_hidden(prompt, mask, None, **kw)
+        step_fn.last_design = (analysis, cond)          # bench.py --dump-outputs
         if not pipeline:
             torch.cuda.synchronize()
         t1 = time.perf_counter()

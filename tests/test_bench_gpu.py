@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -17,13 +18,14 @@ SHARED = dict(LLAMOLE_BENCH_SHARED_GPU="1", LLAMOLE_DIST_BACKEND="gloo")
 TINY_DIT = ["--hidden", "128", "--depth", "2", "--heads", "4", "--T", "10"]
 
 
-def _run(extra, env_extra, workload="graphdit", timeout=600):
+def _run(extra, env_extra, workload="graphdit", timeout=600, full=True):
+    """full: the tests below read the roofline objects and idle-GPU figures, which only `bench.py --full` measures."""
     env = dict(os.environ, **env_extra)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LLAMOLE_BENCH_FAIL_RANK"):
         if k not in env_extra:
             env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload] + TINY_DIT + ["--steps", "1", "--warmup", "1",
-                                                                                                 "--no-cpu-baseline"] + extra
+                                                                                                 "--no-cpu-baseline"] + (["--full"] if full else []) + extra
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
 
 
@@ -177,3 +179,44 @@ def test_bench_under_torch_distributed_run():
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["warmup"] == 1 and d["config"]["gathered_molecules"] == 4
+
+
+# ---- a plain run (no --full): set-up, warm-up, the timed steps, the line; --dump-outputs writes what the last timed step computed
+FULL_ONLY = {"roofline", "roofline_token", "roofline_graphdit", "denoise_step_ms", "step_roofline", "cpu_baseline", "graph_side_ms"}
+
+
+def _dump(path):
+    return {f[:-len(".npy")]: np.load(os.path.join(path, f)) for f in sorted(os.listdir(path)) if f.endswith(".npy")}
+
+
+def test_bench_plain_run_dumps_the_last_step_the_same_in_two_processes(tmp_path):
+    dumps = []
+    for k in range(2):
+        out = str(tmp_path / f"run{k}")
+        d = _line(_run(["--batch", "2", "--steps", "3", "--dump-outputs", out] + E2E_TINY, {}, workload="e2e", full=False))
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "molecules/s" and d["dtype"] == "bf16" and d["higher_is_better"]
+        assert d["ms_per_step"] * d["steps"] == pytest.approx(d["rank_seconds"][0] * 1e3, rel=1e-2) and d["value"] > 0
+        assert not FULL_ONLY & set(d), FULL_ONLY & set(d)
+        dumps.append(_dump(out))
+    a, b = dumps
+    assert set(a) == {"atom_types", "edge_types", "n_atoms", "analysis_tokens", "condition"}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["atom_types"].shape == (2, 16) and a["edge_types"].shape == (2, 16, 16) and a["condition"].shape == (2, 768)
+    assert (a["n_atoms"] == 16).all() and a["atom_types"].min() >= 0 and (a["edge_types"] == a["edge_types"].transpose(0, 2, 1)).all()
+    assert a["analysis_tokens"].shape[0] == 2 and 1 <= a["analysis_tokens"].shape[1] <= 8
+    for k in a:          # seeded inputs, a seed fixes the sampling: the same arrays from a fresh process
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+
+
+@pytest.mark.parametrize("workload", ["retro", "sft"])
+def test_bench_plain_run_dumps_retro_and_sft(tmp_path, workload):
+    extra = RETRO_TINY if workload == "retro" else SFT_TINY
+    d = _line(_run(extra + ["--dump-outputs", str(tmp_path)], {}, workload=workload, full=False))
+    assert not FULL_ONLY & set(d), FULL_ONLY & set(d)
+    got = _dump(str(tmp_path))
+    if workload == "retro":
+        assert got["route_records"].shape == (3, 3) and got["route_records"].dtype == np.float32
+        assert got["route_records"][:, 0].sum() == d["routes_found"] and got["design_atom_types"].shape == (3, 16)
+    else:
+        assert {"loss", "retro_loss"} <= set(got) and all(v.dtype == np.float64 and v.shape == (1,) for v in got.values())
+        assert got["loss"][0] == d["loss"]

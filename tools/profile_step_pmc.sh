@@ -23,7 +23,7 @@ if [ -z "${SKIP_TRACE:-}" ]; then
   db=$(find "$work/kt" -name '*.db' | head -1)
   [ -n "$db" ] && python3 "$root/tools/rocpd_stats.py" "$db" "$out/${tag}_kernel_stats.csv" "$out/${tag}_kernel_gaps.csv" > /dev/null
   # the step time of record comes from an UNPROFILED run of the same command (tracing inflates it)
-  python3 "$root/bench.py" --workload graphdit --steps 3 --warmup 1 --no-graph --no-cpu-baseline "$@" 2>/dev/null | grep '^{' | tail -1 > "$out/${tag}_bench.json"
+  python3 "$root/bench.py" --workload graphdit --steps 3 --warmup 1 --no-graph --full --no-cpu-baseline "$@" 2>/dev/null | grep '^{' | tail -1 > "$out/${tag}_bench.json"
 fi
 for ctr in ${PMC_COUNTERS:-MfmaUtil FETCH_SIZE WRITE_SIZE}; do
   for attempt in 1 2 3; do      # counter collection segfaults now and then on this image: retry the pass in a fresh directory

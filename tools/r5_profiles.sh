@@ -7,15 +7,15 @@ bash tools/profile_bench.sh r5_e2e_b1 --steps 5 --warmup 2 > /dev/null 2>&1
 bash tools/profile_bench.sh r5_graphdit_b1_step --workload graphdit --batch 1 --steps 3 --warmup 1 > /dev/null 2>&1
 bash tools/profile_bench.sh r5_graphdit_b8_step --workload graphdit --steps 3 --warmup 1 > /dev/null 2>&1
 # ---- bench lines
-python bench.py 2>/dev/null | grep '^{' > "$out/r5_bench_e2e.json"
-python bench.py --workload graphdit --steps 3 --warmup 1 2>/dev/null | grep '^{' > "$out/r5_bench_graphdit_b8.json"
-python bench.py --workload graphdit --batch 1 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | grep '^{' > "$out/r5_bench_graphdit_b1.json"
-python bench.py --workload graphdit --batch 16 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | grep '^{' > "$out/r5_bench_graphdit_b16.json"
+python bench.py --full 2>/dev/null | grep '^{' > "$out/r5_bench_e2e.json"
+python bench.py --workload graphdit --steps 3 --warmup 1 --full 2>/dev/null | grep '^{' > "$out/r5_bench_graphdit_b8.json"
+python bench.py --workload graphdit --batch 1 --steps 3 --warmup 1 --no-cpu-baseline --full 2>/dev/null | grep '^{' > "$out/r5_bench_graphdit_b1.json"
+python bench.py --workload graphdit --batch 16 --steps 3 --warmup 1 --no-cpu-baseline --full 2>/dev/null | grep '^{' > "$out/r5_bench_graphdit_b16.json"
 # the upstream Graph-DiT width (VERDICT r4 next #1c): hidden 1152, 16 heads of 72
-python bench.py --workload graphdit --hidden 1152 --depth 28 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | grep '^{' > "$out/r5_bench_graphdit_h1152_b8.json"
-python bench.py --workload graphdit --hidden 1152 --depth 28 --batch 1 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | grep '^{' > "$out/r5_bench_graphdit_h1152_b1.json"
-python bench.py --workload sft 2>/dev/null | grep '^{' > "$out/r5_bench_sft.json"
-python bench.py --workload retro --steps 2 --warmup 1 2>/dev/null | grep '^{' > "$out/r5_bench_retro.json"
+python bench.py --workload graphdit --hidden 1152 --depth 28 --steps 3 --warmup 1 --no-cpu-baseline --full 2>/dev/null | grep '^{' > "$out/r5_bench_graphdit_h1152_b8.json"
+python bench.py --workload graphdit --hidden 1152 --depth 28 --batch 1 --steps 3 --warmup 1 --no-cpu-baseline --full 2>/dev/null | grep '^{' > "$out/r5_bench_graphdit_h1152_b1.json"
+python bench.py --workload sft --full 2>/dev/null | grep '^{' > "$out/r5_bench_sft.json"
+python bench.py --workload retro --steps 2 --warmup 1 --full 2>/dev/null | grep '^{' > "$out/r5_bench_retro.json"
 for f in r5_bench_e2e r5_bench_graphdit_b8 r5_bench_graphdit_b1 r5_bench_graphdit_b16 r5_bench_graphdit_h1152_b8 r5_bench_graphdit_h1152_b1 r5_bench_sft r5_bench_retro; do python - <<PY
 import json
 try:

@@ -7,17 +7,17 @@ export LL_PMC_ROUND=r6
 bash tools/profile_bench.sh r6_e2e_b1 --steps 5 --warmup 2 > /dev/null 2>&1
 bash tools/profile_bench.sh r6_llama64 --llm llama-3.1-8b --total-prompts 64 --steps 2 --warmup 1 > /dev/null 2>&1
 # ---- bench lines
-python bench.py 2>/dev/null | grep '^{' > "$out/r6_bench_e2e.json"
-python bench.py --llm llama-3.1-8b --total-prompts 64 --steps 4 --warmup 1 2>/dev/null | grep '^{' > "$out/r6_bench_llama_total64_n1.json"
-python bench.py --llm llama-3.1-8b --total-prompts 64 --steps 4 --warmup 1 --no-pipeline --no-cpu-baseline 2>/dev/null | grep '^{' > "$out/r6_bench_llama_total64_n1_nopipeline.json"
-python bench.py --llm qwen2-7b --total-prompts 64 --steps 4 --warmup 1 --no-cpu-baseline 2>/dev/null | grep '^{' > "$out/r6_bench_qwen_total64_n1.json"
-python bench.py --llm llama-3.1-8b --total-prompts 64 --batch 32 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | grep '^{' > "$out/r6_bench_llama_total64_batch32.json"
-python bench.py --batch 16 --steps 4 --warmup 1 --no-cpu-baseline 2>/dev/null | grep '^{' > "$out/r6_bench_e2e_b16.json"
-python bench.py --workload graphdit --steps 3 --warmup 1 2>/dev/null | grep '^{' > "$out/r6_bench_graphdit_b8.json"
-python bench.py --workload graphdit --batch 1 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | grep '^{' > "$out/r6_bench_graphdit_b1.json"
-python bench.py --workload graphdit --batch 64 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | grep '^{' > "$out/r6_bench_graphdit_b64.json"
-python bench.py --workload sft 2>/dev/null | grep '^{' > "$out/r6_bench_sft.json"
-python bench.py --workload retro --steps 2 --warmup 1 2>/dev/null | grep '^{' > "$out/r6_bench_retro.json"
+python bench.py --full 2>/dev/null | grep '^{' > "$out/r6_bench_e2e.json"
+python bench.py --llm llama-3.1-8b --total-prompts 64 --steps 4 --warmup 1 --full 2>/dev/null | grep '^{' > "$out/r6_bench_llama_total64_n1.json"
+python bench.py --llm llama-3.1-8b --total-prompts 64 --steps 4 --warmup 1 --no-pipeline --no-cpu-baseline --full 2>/dev/null | grep '^{' > "$out/r6_bench_llama_total64_n1_nopipeline.json"
+python bench.py --llm qwen2-7b --total-prompts 64 --steps 4 --warmup 1 --no-cpu-baseline --full 2>/dev/null | grep '^{' > "$out/r6_bench_qwen_total64_n1.json"
+python bench.py --llm llama-3.1-8b --total-prompts 64 --batch 32 --steps 3 --warmup 1 --no-cpu-baseline --full 2>/dev/null | grep '^{' > "$out/r6_bench_llama_total64_batch32.json"
+python bench.py --batch 16 --steps 4 --warmup 1 --no-cpu-baseline --full 2>/dev/null | grep '^{' > "$out/r6_bench_e2e_b16.json"
+python bench.py --workload graphdit --steps 3 --warmup 1 --full 2>/dev/null | grep '^{' > "$out/r6_bench_graphdit_b8.json"
+python bench.py --workload graphdit --batch 1 --steps 3 --warmup 1 --no-cpu-baseline --full 2>/dev/null | grep '^{' > "$out/r6_bench_graphdit_b1.json"
+python bench.py --workload graphdit --batch 64 --steps 3 --warmup 1 --no-cpu-baseline --full 2>/dev/null | grep '^{' > "$out/r6_bench_graphdit_b64.json"
+python bench.py --workload sft --full 2>/dev/null | grep '^{' > "$out/r6_bench_sft.json"
+python bench.py --workload retro --steps 2 --warmup 1 --full 2>/dev/null | grep '^{' > "$out/r6_bench_retro.json"
 for f in r6_bench_e2e r6_bench_llama_total64_n1 r6_bench_llama_total64_n1_nopipeline r6_bench_qwen_total64_n1 r6_bench_llama_total64_batch32 r6_bench_e2e_b16 r6_bench_graphdit_b8 r6_bench_graphdit_b1 r6_bench_graphdit_b64 r6_bench_sft r6_bench_retro; do python - <<PY
 import json
 try:
