@@ -344,6 +344,21 @@ int ll_sample_token_topk_ws_bf16(const void *logits, int64_t ld, int B, int V, f
                                  int64_t *out_tokens, int64_t ld_out, int max_new, int64_t *step, int64_t *posid, int64_t *pos, int advance,
                                  uint64_t *dbg, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Repetition penalty (HF RepetitionPenaltyLogitsProcessor, ahead of the warpers): a per-row set of the tokens seen so far on the device.
+ * ll_seen_set_bytes(B, V, cap): bytes of the set for B rows, at most cap distinct tokens per row (a deduplicated list of ids, a bitmap
+ *     of ceil(V/32) words and the sampler's scratch).
+ * ll_seen_set_init : one launch; seeds row b from input_ids[b*ld .. b*ld + P) (pads included; P = 0: empty; ids outside [0, V) ignored).
+ * ll_sample_token_penalty_bf16 : ll_sample_token_topk_bf16 on the penalised f32 logits -- every token of the row's set gets
+ *     x < 0 ? x * penalty : x / penalty (inf / NaN sanitised as the raw logit is) before temperature, top-k, top-p, multinomial / argmax --
+ *     and the emitted token (pad of a stopped row included) joins the set.  penalty > 0; penalty == 1: the set is kept but nothing is
+ *     penalised (the same tokens as ll_sample_token_topk_ws_bf16 for every seed, as is an empty set). */
+int64_t ll_seen_set_bytes(int B, int V, int cap);
+int ll_seen_set_init(void *seen, int64_t seen_bytes, int B, int V, int cap, const int64_t *input_ids, int64_t ld, int P, void *stream);
+int ll_sample_token_penalty_bf16(const void *logits, int64_t ld, int B, int V, float inv_temp, float top_p, int top_k, int greedy,
+                                 const int64_t *seed, const int64_t *eos, int n_eos, int64_t pad, void *done, int64_t *tok,
+                                 int64_t *out_tokens, int64_t ld_out, int max_new, int64_t *step, int64_t *posid, int64_t *pos, int advance,
+                                 void *seen, int64_t seen_bytes, int cap, float penalty, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,10 @@ SIGNATURES = {
     "ll_sample_token_topk_bf16": (_I, [_P, _I64, _I, _I, _F, _F, _I, _I, _P, _P, _I, _I64, _P, _P, _P, _I64, _I, _P, _P, _P, _I, _P, _P]),
     "ll_sample_workspace_bytes": (_I64, [_I]),
     "ll_sample_token_topk_ws_bf16": (_I, [_P, _I64, _I, _I, _F, _F, _I, _I, _P, _P, _I, _I64, _P, _P, _P, _I64, _I, _P, _P, _P, _I, _P, _P, _I64, _P]),
+    "ll_seen_set_bytes": (_I64, [_I, _I, _I]),
+    "ll_seen_set_init": (_I, [_P, _I64, _I, _I, _I, _P, _I64, _I, _P]),
+    "ll_sample_token_penalty_bf16": (_I, [_P, _I64, _I, _I, _F, _F, _I, _I, _P, _P, _I, _I64, _P, _P, _P, _I64, _I, _P, _P, _P, _I,
+                                          _P, _I64, _I, _F, _P]),
 }
 
 # include/llamole_hip_tuning.h: exported by libllamole_hip_tuning.so only (the LL_TUNING=1 build of the same sources)

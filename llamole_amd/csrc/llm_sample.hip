@@ -420,15 +420,9 @@ __device__ __forceinline__ bool sample_fast(SampleLds &L, const SampleArgs &a, i
     return true;
 }
 
+// ---- stages of the one-workgroup sampler, shared by sample_token_kernel and sample_token_pen_kernel
 template <int CH>
-__global__ __launch_bounds__(1024) void sample_token_kernel(SampleArgs a) {
-    __shared__ SampleLds L;
-    sample_prefetch(L, a, blockIdx.x, threadIdx.x);
-    if (a.cand_total && sample_fast<CH>(L, a, blockIdx.x, threadIdx.x, threadIdx.x & 63, threadIdx.x >> 6)) return;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bf16_t *row = a.logits + (int64_t)b * a.ld;
-    const int nchunk = a.V / 8;
-    uint32_t w[CH][4];   // two 16-bit keys per word; key 0 = no element
+__device__ __forceinline__ void sample_load(uint32_t (&w)[CH][4], const bf16_t *row, int tid, int nchunk) {
 #pragma unroll
     for (int k = 0; k < CH; ++k) {
         const int c = tid + k * 1024;
@@ -436,13 +430,11 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(SampleArgs a) {
         if (c < nchunk) v = *reinterpret_cast<const uint4 *>(row + (int64_t)c * 8);
         w[k][0] = v.x; w[k][1] = v.y; w[k][2] = v.z; w[k][3] = v.w;
     }
-    if (!a.greedy) {
-#pragma unroll
-        for (int i = 0; i < SAMPLE_BPT; ++i) L.cnt[i * 1024 + tid] = 0;
-    }
-    if (tid == 0) { L.tail = 0; L.d = 0; L.tok = 0; L.dk = 0xffffffffu; L.Zk = 0; L.klo = 0; }
-    for (int i = tid; i < SAMPLE_TM_BINS + 1; i += 1024) L.tmh[i] = 0;
-    reg_fence<CH>(w);
+}
+
+// the thread's keys in place of its bf16 logits; returns the thread maximum
+template <int CH, bool MASK>
+__device__ __forceinline__ uint32_t sample_keys(uint32_t (&w)[CH][4], int tid, int nchunk, const uint32_t (&mb)[(CH + 3) / 4]) {
     // keys: the finite conversion for every pair (7 VALU instructions per pair instead of ~25 with the inf / NaN canonicalisation);
     // the inf / NaN test is taken per 16-byte chunk and such a chunk (rare) is converted again; the all-ones fill past the end of the
     // row becomes key 0 = no element
@@ -454,95 +446,114 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(SampleArgs a) {
         if (((pair_special(r0) | pair_special(r1) | pair_special(r2) | pair_special(r3)) & 0x80008000u) && tid + k * 1024 < nchunk) {
             k0 = keys_of_pair(r0); k1 = keys_of_pair(r1); k2_ = keys_of_pair(r2); k3 = keys_of_pair(r3);
         }
+        if constexpr (MASK) {            // seen tokens (bit set in their 8-token chunk's byte of mb) leave: key 0 = no element
+            const uint32_t m8 = (mb[k >> 2] >> (8 * (k & 3))) & 0xffu;
+            if (m8) {
+                k0 &= ((m8 & 1u) ? 0xffff0000u : ~0u) & ((m8 & 2u) ? 0x0000ffffu : ~0u);
+                k1 &= ((m8 & 4u) ? 0xffff0000u : ~0u) & ((m8 & 8u) ? 0x0000ffffu : ~0u);
+                k2_ &= ((m8 & 16u) ? 0xffff0000u : ~0u) & ((m8 & 32u) ? 0x0000ffffu : ~0u);
+                k3 &= ((m8 & 64u) ? 0xffff0000u : ~0u) & ((m8 & 128u) ? 0x0000ffffu : ~0u);
+            }
+        }
         w[k][0] = k0; w[k][1] = k1; w[k][2] = k2_; w[k][3] = k3;
         kmaxp = pk_max_u16(pk_max_u16(kmaxp, k0), pk_max_u16(pk_max_u16(k1, k2_), k3));
         __builtin_amdgcn_sched_barrier(0);
     }
-    const uint32_t kmaxi = max(kmaxp & 0xffffu, kmaxp >> 16);
+    return max(kmaxp & 0xffffu, kmaxp >> 16);
+}
+
+__device__ __forceinline__ uint32_t sample_kmax(SampleLds &L, uint32_t kmaxi, int lane, int wave) {
     float kmaxf = wave_max((float)kmaxi);
     if (lane == 0) L.redf[wave] = kmaxf;
     __syncthreads();
     float km = L.redf[0];
 #pragma unroll
     for (int i = 1; i < 16; ++i) km = fmaxf(km, L.redf[i]);
-    const uint32_t kmax = __builtin_amdgcn_readfirstlane((uint32_t)km);      // uniform values live in scalar registers
-    const float m = scaled(kmax, a.inv_temp);
-    uint32_t k2 = kmax;      // the value to pick a token of
-    uint32_t rank = 0;
-    if (!a.greedy) {
-        // ---- 1b. with top-k on, a lower bound of the k-th largest key: at least k THREADS hold a key >= klo, so nothing below klo
-        // survives TopKLogitsWarper and it need not be counted.  klo = lower edge of the 32-key bin in which the count of thread
-        // maxima, taken from the row maximum down, reaches k (0 = no bound: k > 1024 threads, or the maxima leave the window).
-        // The dbg tap reports the mass of the whole row, so it counts everything.
-        uint32_t klo = 0;
-        if (a.top_k > 0 && a.top_k <= 1024 && !a.dbg) {
-            const uint32_t dm = kmax - kmaxi;
-            if (kmaxi) atomicAdd(&L.tmh[dm < (uint32_t)SAMPLE_W ? (dm >> 5) : SAMPLE_TM_BINS], 1u);
-            __syncthreads();
-            const uint32_t c0 = 2 * tid < SAMPLE_TM_BINS ? L.tmh[2 * tid] : 0u, c1 = 2 * tid + 1 < SAMPLE_TM_BINS ? L.tmh[2 * tid + 1] : 0u;
-            uint32_t inct = c0 + c1;
+    return __builtin_amdgcn_readfirstlane((uint32_t)km);      // uniform values live in scalar registers
+}
+
+__device__ __forceinline__ uint32_t sample_klo(SampleLds &L, const SampleArgs &a, int tid, int lane, int wave, uint32_t kmax, uint32_t kmaxi) {
+    // ---- 1b. with top-k on, a lower bound of the k-th largest key: at least k THREADS hold a key >= klo, so nothing below klo
+    // survives TopKLogitsWarper and it need not be counted.  klo = lower edge of the 32-key bin in which the count of thread
+    // maxima, taken from the row maximum down, reaches k (0 = no bound: k > 1024 threads, or the maxima leave the window).
+    // The dbg tap reports the mass of the whole row, so it counts everything.
+    uint32_t klo = 0;
+    if (a.top_k > 0 && a.top_k <= 1024 && !a.dbg) {
+        const uint32_t dm = kmax - kmaxi;
+        if (kmaxi) atomicAdd(&L.tmh[dm < (uint32_t)SAMPLE_W ? (dm >> 5) : SAMPLE_TM_BINS], 1u);
+        __syncthreads();
+        const uint32_t c0 = 2 * tid < SAMPLE_TM_BINS ? L.tmh[2 * tid] : 0u, c1 = 2 * tid + 1 < SAMPLE_TM_BINS ? L.tmh[2 * tid + 1] : 0u;
+        uint32_t inct = c0 + c1;
 #pragma unroll
-            for (int dd = 1; dd < 64; dd <<= 1) {
-                const uint32_t o = __shfl_up(inct, dd, 64);
-                if (lane >= dd) inct += o;
-            }
-            if (lane == 63) L.redu[wave] = inct;
-            __syncthreads();
-            uint32_t baset = 0;
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-                if (i < wave) baset += L.redu[i];
-            const uint32_t exclt = baset + inct - c0 - c1, kk = (uint32_t)a.top_k;
-            if (exclt < kk && exclt + c0 + c1 >= kk) {
-                const uint32_t bin = exclt + c0 >= kk ? 2 * tid : 2 * tid + 1;
-                const uint32_t dlow = bin * 32 + 31;                 // the lowest key of that bin is kmax - dlow
-                L.klo = dlow < kmax ? kmax - dlow : 1u;
-            }
-            __syncthreads();
-            klo = __builtin_amdgcn_readfirstlane(L.klo);
+        for (int dd = 1; dd < 64; dd <<= 1) {
+            const uint32_t o = __shfl_up(inct, dd, 64);
+            if (lane >= dd) inct += o;
         }
-        // ---- 2. exact count histogram over the key window [kmax - W + 1, kmax]; anything below goes to one tail mass
-        reg_fence<CH>(w);
-        if (klo) {
-            // nothing below klo is counted and the tail mass is not needed (it only enters Z, which top-k replaces by the survivors'
-            // mass): one packed compare per pair of keys, the counting itself is rare
-            const uint32_t below = (klo - 1u) * 0x00010001u;
+        if (lane == 63) L.redu[wave] = inct;
+        __syncthreads();
+        uint32_t baset = 0;
 #pragma unroll
-            for (int k = 0; k < CH; ++k) {
+        for (int i = 0; i < 16; ++i)
+            if (i < wave) baset += L.redu[i];
+        const uint32_t exclt = baset + inct - c0 - c1, kk = (uint32_t)a.top_k;
+        if (exclt < kk && exclt + c0 + c1 >= kk) {
+            const uint32_t bin = exclt + c0 >= kk ? 2 * tid : 2 * tid + 1;
+            const uint32_t dlow = bin * 32 + 31;                 // the lowest key of that bin is kmax - dlow
+            L.klo = dlow < kmax ? kmax - dlow : 1u;
+        }
+        __syncthreads();
+        klo = __builtin_amdgcn_readfirstlane(L.klo);
+    }
+    return klo;
+}
+
+template <int CH>
+__device__ __forceinline__ void sample_hist(SampleLds &L, const SampleArgs &a, uint32_t (&w)[CH][4], uint32_t kmax, uint32_t klo, float m) {
+    // ---- 2. exact count histogram over the key window [kmax - W + 1, kmax]; anything below goes to one tail mass
+    reg_fence<CH>(w);
+    if (klo) {
+        // nothing below klo is counted and the tail mass is not needed (it only enters Z, which top-k replaces by the survivors'
+        // mass): one packed compare per pair of keys, the counting itself is rare
+        const uint32_t below = (klo - 1u) * 0x00010001u;
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const uint32_t kk = w[k][t];
-                    if (pk_max_u16(kk, below) != below) {
-                        if ((kk & 0xffffu) >= klo) atomicAdd(&L.cnt[kmax - (kk & 0xffffu)], 1u);
-                        if ((kk >> 16) >= klo) atomicAdd(&L.cnt[kmax - (kk >> 16)], 1u);
-                    }
+        for (int k = 0; k < CH; ++k) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const uint32_t kk = w[k][t];
+                if (pk_max_u16(kk, below) != below) {
+                    if ((kk & 0xffffu) >= klo) atomicAdd(&L.cnt[kmax - (kk & 0xffffu)], 1u);
+                    if ((kk >> 16) >= klo) atomicAdd(&L.cnt[kmax - (kk >> 16)], 1u);
                 }
-                __builtin_amdgcn_sched_barrier(0);
             }
-        } else {
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    } else {
 #pragma unroll
-            for (int k = 0; k < CH; ++k) {
+        for (int k = 0; k < CH; ++k) {
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
+            for (int t = 0; t < 4; ++t) {
 #pragma unroll
-                    for (int hh = 0; hh < 2; ++hh) {
-                        const uint32_t key = hh ? (w[k][t] >> 16) : (w[k][t] & 0xffffu);
-                        const uint32_t d = kmax - key;
-                        if (key) {
-                            if (d < (uint32_t)SAMPLE_W) atomicAdd(&L.cnt[d], 1u);
-                            else {
-                                const unsigned long long q = mass_of(key, a.inv_temp, m);
-                                if (q) atomicAdd(&L.tail, q);
-                            }
+                for (int hh = 0; hh < 2; ++hh) {
+                    const uint32_t key = hh ? (w[k][t] >> 16) : (w[k][t] & 0xffffu);
+                    const uint32_t d = kmax - key;
+                    if (key) {
+                        if (d < (uint32_t)SAMPLE_W) atomicAdd(&L.cnt[d], 1u);
+                        else {
+                            const unsigned long long q = mass_of(key, a.inv_temp, m);
+                            if (q) atomicAdd(&L.tail, q);
                         }
                     }
                 }
-                __builtin_amdgcn_sched_barrier(0);
             }
+            __builtin_amdgcn_sched_barrier(0);
         }
-        __syncthreads();
-        nucleus_scan(L, a, b, tid, lane, wave, kmax, klo, m, k2, rank);
     }
+}
+
+// L.tok (thread 0 writes it under greedy, the finder otherwise)
+template <int CH>
+__device__ __forceinline__ void sample_pick(SampleLds &L, const SampleArgs &a, uint32_t (&w)[CH][4], int tid, int lane, int wave, uint32_t k2,
+                                            uint32_t rank) {
     // ---- 5. the rank-th token whose key is k2 (greedy: the lowest index holding the maximum, like torch.argmax)
     reg_fence<CH>(w);
     uint32_t cntm = 0, minidx = 0xffffffffu;
@@ -600,7 +611,383 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(SampleArgs a) {
             L.tok = found;
         }
     }
+}
+
+template <int CH>
+__global__ __launch_bounds__(1024) void sample_token_kernel(SampleArgs a) {
+    __shared__ SampleLds L;
+    sample_prefetch(L, a, blockIdx.x, threadIdx.x);
+    if (a.cand_total && sample_fast<CH>(L, a, blockIdx.x, threadIdx.x, threadIdx.x & 63, threadIdx.x >> 6)) return;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bf16_t *row = a.logits + (int64_t)b * a.ld;
+    const int nchunk = a.V / 8;
+    uint32_t w[CH][4];   // two 16-bit keys per word; key 0 = no element
+    sample_load<CH>(w, row, tid, nchunk);
+    if (!a.greedy) {
+#pragma unroll
+        for (int i = 0; i < SAMPLE_BPT; ++i) L.cnt[i * 1024 + tid] = 0;
+    }
+    if (tid == 0) { L.tail = 0; L.d = 0; L.tok = 0; L.dk = 0xffffffffu; L.Zk = 0; L.klo = 0; }
+    for (int i = tid; i < SAMPLE_TM_BINS + 1; i += 1024) L.tmh[i] = 0;
+    reg_fence<CH>(w);
+    const uint32_t nomask[(CH + 3) / 4] = {};
+    const uint32_t kmaxi = sample_keys<CH, false>(w, tid, nchunk, nomask);
+    const uint32_t kmax = sample_kmax(L, kmaxi, lane, wave);
+    const float m = scaled(kmax, a.inv_temp);
+    uint32_t k2 = kmax;      // the value to pick a token of
+    uint32_t rank = 0;
+    if (!a.greedy) {
+        const uint32_t klo = sample_klo(L, a, tid, lane, wave, kmax, kmaxi);
+        sample_hist<CH>(L, a, w, kmax, klo, m);
+        __syncthreads();
+        nucleus_scan(L, a, b, tid, lane, wave, kmax, klo, m, k2, rank);
+    }
+    sample_pick<CH>(L, a, w, tid, lane, wave, k2, rank);
     sample_finish(L, a, b, tid);
+}
+
+
+// ---------------------------------------------------------------- repetition penalty (HF RepetitionPenaltyLogitsProcessor)
+// Per row, a set of the tokens seen so far (ll_seen_set_init seeds it from input_ids, the penalised sampler adds each token it
+// emits): 16-byte header (count), a deduplicated list of cap token ids, a bitmap of ceil(V/32) words, and the penalised sampler's
+// scratch (entries unsorted / sorted: keys and tokens, cap each; prefix masses, cap + 1).  Only the row's own workgroup touches it.
+__host__ __device__ inline int64_t seen_em_offset(int V, int cap) {
+    return (16 + 4 * (int64_t)cap + 4 * (int64_t)((V + 31) / 32) + 16 * (int64_t)cap + 15) & ~(int64_t)15;
+}
+__host__ __device__ inline int64_t seen_row_bytes(int V, int cap) { return (seen_em_offset(V, cap) + 8 * ((int64_t)cap + 1) + 15) & ~(int64_t)15; }
+
+__global__ __launch_bounds__(1024) void seen_init_kernel(unsigned char *__restrict__ ws, int64_t rb, int V, int cap, const long long *__restrict__ ids,
+                                                         int64_t ld, int P) {
+    const int b = blockIdx.x;
+    uint32_t *hdr = reinterpret_cast<uint32_t *>(ws + (int64_t)b * rb), *list = hdr + 4, *bm = list + cap;
+    const int nw = (V + 31) / 32;
+    for (int i = threadIdx.x; i < nw; i += 1024) bm[i] = 0u;
+    if (threadIdx.x == 0) hdr[0] = 0u;
+    __syncthreads();
+    for (int j = threadIdx.x; j < P; j += 1024) {
+        const long long t = ids[(int64_t)b * ld + j];
+        if (t < 0 || t >= V) continue;
+        const uint32_t bit = 1u << (t & 31);
+        if (!(atomicOr(&bm[t >> 5], bit) & bit)) {
+            const uint32_t i = atomicAdd(&hdr[0], 1u);
+            if (i < (uint32_t)cap) list[i] = (uint32_t)t;
+            else atomicAnd(&bm[t >> 5], ~bit);          // past the capacity (the caller sizes it): left unpenalised rather than lost
+        }
+    }
+}
+
+// 32-bit order-preserving keys of f32 values; a bf16 key k is the top half of the key of its value
+__device__ __forceinline__ uint32_t k32_of_f(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+__device__ __forceinline__ float f_of_k32(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+__device__ __forceinline__ uint32_t k32_of_key(uint32_t k) { return (k << 16) | ((k & 0x8000u) ? 0u : 0xffffu); }
+// HF's formula on the f32 copy of a bf16 logit x: x < 0 ? x * p : x / p; inf / NaN are sanitised as the sampler sanitises the raw logit;
+// an overflow to +-inf becomes +-FLT_MAX (InfNanRemoveLogitsProcessor, which runs behind the penalty)
+__device__ __forceinline__ uint32_t pen_k32(uint32_t x, float p) {
+    if (((x >> 7) & 0xffu) == 0xffu) return k32_of_key(key_of(x));
+    float f = __uint_as_float(x << 16);
+    f = f < 0.f ? __fmul_rn(f, p) : __fdiv_rn(f, p);
+    return k32_of_f(fminf(fmaxf(f, -3.40282347e38f), 3.40282347e38f));
+}
+__device__ __forceinline__ unsigned long long mass_k32(uint32_t k, float inv_temp, float m) {
+    return (unsigned long long)(__expf(fminf(fmaxf(f_of_k32(k) * inv_temp, -3.0e38f), 3.0e38f) - m) * 1099511627776.0f);
+}
+// sorted entries (key descending): the first index whose key is <= v
+__device__ __forceinline__ uint32_t ent_lb(const uint32_t *sk, uint32_t n, uint32_t v) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (sk[mid] > v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+struct SampleArgsPen {
+    SampleArgs s;
+    unsigned char *seen;       // [B] rows of seen_row_bytes(V, cap)
+    int64_t rb;
+    int cap;
+    float pen;
+    int pen_on;                // pen != 1: penalise (the set is kept current either way)
+};
+
+struct SampleLdsPen : SampleLds {
+    unsigned long long pexcl[1024];      // bin mass above each thread's first bin (the bin count above it goes to tmh)
+    unsigned long long Zb, emax, Zk2;
+    unsigned int Cb, ns, ekmax, cut, tau, eidx;
+};
+
+// Mass and count of the histogram's bins whose value is strictly above the 32-bit key v (bins: see nucleus_scan)
+__device__ __forceinline__ void bins_above(const SampleLdsPen &L, uint32_t v, uint32_t kmax, int bpt, float inv_temp, float m,
+                                           unsigned long long &A, uint32_t &C) {
+    A = 0; C = 0;
+    const int top = (int)(v >> 16), d = (int)kmax - top;
+    if (kmax == 0u || d < 0) return;
+    const int dl = d + (k32_of_key((uint32_t)top) > v ? 1 : 0);        // bins [0, dl) lie above v
+    if (dl >= bpt * 1024) { A = L.Zb; C = L.Cb; return; }
+    const int t = dl / bpt;
+    A = L.pexcl[t]; C = L.tmh[t];
+    for (int i = t * bpt; i < dl; ++i) {
+        const uint32_t c = L.cnt[i];
+        if (c && (uint32_t)i < kmax) { A += (unsigned long long)c * mass_of(kmax - i, inv_temp, m); C += c; }
+    }
+}
+
+// nucleus_scan over the histogram of the UNSEEN tokens' keys plus the ns penalised entries (sk / st: 32-bit keys descending, tokens
+// ascending among equal keys; em: exclusive prefix masses).  Every distinct value is a candidate -- a non-empty bin (with the entries
+// tied to it) or a group of equal entries -- that knows the mass A and count C of everything strictly above it: the bin side from the
+// scanned histogram plus em / index at its place in the entries, the entry side from em / index plus bins_above.  Top-k cut, nucleus
+// boundary and draw are then each one predicate per candidate.  Result: *eidx = entry index, or ~0 and (k2, rank) in the bf16 tokens.
+__device__ __forceinline__ void nucleus_scan_pen(SampleLdsPen &L, const SampleArgs &a, int b, int tid, int lane, int wave, uint32_t kmax,
+                                                 uint32_t klo, float m, uint32_t ns, const uint32_t *sk, const unsigned long long *em,
+                                                 uint32_t &k2, uint32_t &rank, uint32_t &eidx) {
+    const int bpt = klo ? (int)((kmax - klo) >> 10) + 1 : SAMPLE_BPT;
+    const int d0 = tid * bpt;
+    unsigned long long lsum = 0;
+    uint32_t lc = 0;
+    for (int i = 0; i < bpt; ++i) {
+        const uint32_t c = L.cnt[d0 + i];
+        if (c && (uint32_t)(d0 + i) < kmax) { lsum += (unsigned long long)c * mass_of(kmax - (d0 + i), a.inv_temp, m); lc += c; }
+    }
+    unsigned long long inc = lsum;
+    uint32_t incc = lc;
+#pragma unroll
+    for (int dd = 1; dd < 64; dd <<= 1) {
+        const unsigned long long o = __shfl_up(inc, dd, 64);
+        const uint32_t oc = __shfl_up(incc, dd, 64);
+        if (lane >= dd) { inc += o; incc += oc; }
+    }
+    if (lane == 63) { L.wsum[wave] = inc; L.redu[wave] = incc; }
+    __syncthreads();
+    unsigned long long base = 0, Zb = 0;
+    uint32_t basec = 0, Cb = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        if (i < wave) { base += L.wsum[i]; basec += L.redu[i]; }
+        Zb += L.wsum[i];
+        Cb += L.redu[i];
+    }
+    const unsigned long long excl = base + inc - lsum;
+    const uint32_t exclc = basec + incc - lc;
+    L.pexcl[tid] = excl;
+    L.tmh[tid] = exclc;
+    if (tid == 0) { L.Zb = Zb; L.Cb = Cb; L.cut = 0u; L.tau = 0xffffffffu; L.eidx = 0xffffffffu; L.key = kmax; L.rank = 0; }
+    __syncthreads();
+    const unsigned long long Z = uniform64(L.tail + Zb + em[ns]);
+    const uint32_t vtop = (ns && (kmax == 0u || sk[0] > k32_of_key(kmax))) ? sk[0] : k32_of_key(kmax);
+    // every candidate: f(v, A, C, count, q, bin count, first entry, bin)
+    auto each = [&](auto &&f) {
+        uint32_t p = 0;
+        bool first = true;
+        unsigned long long Ab = excl;
+        uint32_t Cbin = exclc;
+        for (int i = 0; i < bpt; ++i) {
+            const int d = d0 + i;
+            const uint32_t c = L.cnt[d];
+            if (!c || (uint32_t)d >= kmax) continue;
+            const uint32_t v = k32_of_key(kmax - d);
+            if (first) { p = ent_lb(sk, ns, v); first = false; }
+            while (p < ns && sk[p] > v) ++p;
+            uint32_t p2 = p;
+            while (p2 < ns && sk[p2] == v) ++p2;
+            const unsigned long long q = mass_of(kmax - d, a.inv_temp, m);
+            f(v, Ab + em[p], Cbin + p, c + (p2 - p), q, c, p, d);
+            Ab += (unsigned long long)c * q;
+            Cbin += c;
+        }
+        for (uint32_t j = tid; j < ns; j += 1024) {
+            const uint32_t v = sk[j];
+            if (j > 0 && sk[j - 1] == v) continue;
+            const int top = (int)(v >> 16), d = (int)kmax - top;
+            if (kmax && k32_of_key((uint32_t)top) == v && d >= 0 && d < bpt * 1024 && (uint32_t)d < kmax && L.cnt[d]) continue;   // the bin's candidate
+            uint32_t j2 = j + 1;
+            while (j2 < ns && sk[j2] == v) ++j2;
+            unsigned long long A;
+            uint32_t C;
+            bins_above(L, v, kmax, bpt, a.inv_temp, m, A, C);
+            f(v, A + em[j], C + j, j2 - j, mass_k32(v, a.inv_temp, m), 0u, j, -1);
+        }
+    };
+    uint32_t cut = 0;
+    unsigned long long Zk = Z;
+    if (a.top_k > 0) {
+        const uint32_t kk = (uint32_t)a.top_k;
+        each([&](uint32_t v, unsigned long long A, uint32_t C, uint32_t n, unsigned long long q, uint32_t, uint32_t, int) {
+            if (C < kk && C + n >= kk) { L.cut = v; L.Zk2 = A + (unsigned long long)n * q; }
+        });
+        __syncthreads();
+        cut = __builtin_amdgcn_readfirstlane(L.cut);           // 0: fewer than k tokens in the window, nothing is cut
+        if (cut) Zk = uniform64(L.Zk2);
+    }
+    const unsigned long long Tq = a.top_p >= 1.f ? ~0ull : (unsigned long long)((double)a.top_p * (double)Zk);
+    each([&](uint32_t v, unsigned long long A, uint32_t, uint32_t, unsigned long long, uint32_t, uint32_t, int) {
+        if (v >= cut && A < Tq) atomicMin(&L.tau, v);
+    });
+    __syncthreads();
+    uint32_t tau = __builtin_amdgcn_readfirstlane(L.tau);
+    if (tau == 0xffffffffu) tau = vtop;                      // nothing qualifies (top_p = 0): the top value is kept
+    each([&](uint32_t v, unsigned long long A, uint32_t, uint32_t n, unsigned long long q, uint32_t, uint32_t, int) {
+        if (v != tau) return;
+        unsigned long long M = A + (unsigned long long)n * q;   // kept mass: everything down to and including the boundary value
+        if (a.top_p >= 1.f && cut == 0u) M = Z;
+        const unsigned long long sd = (unsigned long long)*a.seed;
+        const unsigned long long st = (unsigned long long)a.step[b];
+        const uint4 rnd = philox4x32(make_uint4((uint32_t)st, (uint32_t)(st >> 32), (uint32_t)b, 0x5A17u),
+                                     make_uint2((uint32_t)sd, (uint32_t)(sd >> 32)));
+        L.R = __umul64hi(((unsigned long long)rnd.x << 32) | rnd.y, M);
+    });
+    if (tid == 0 && vtop != k32_of_key(kmax)) L.eidx = 0u;   // R in the tail mass: the top value (an entry above every bin)
+    __syncthreads();
+    const unsigned long long R = uniform64(L.R);
+    each([&](uint32_t v, unsigned long long A, uint32_t, uint32_t n, unsigned long long q, uint32_t cb, uint32_t p, int d) {
+        if (v < tau || R < A || R - A >= (unsigned long long)n * q) return;
+        unsigned long long r = q ? (R - A) / q : 0;
+        if (r >= n) r = n - 1;
+        if (r < cb) { L.key = kmax - d; L.rank = (uint32_t)r; L.eidx = 0xffffffffu; }
+        else L.eidx = p + (uint32_t)(r - cb);
+    });
+    __syncthreads();
+    k2 = __builtin_amdgcn_readfirstlane(L.key);
+    rank = __builtin_amdgcn_readfirstlane(L.rank);
+    eidx = __builtin_amdgcn_readfirstlane(L.eidx);
+}
+
+// The sampler with HF's repetition penalty: sample_token_kernel's one-workgroup path with the seen tokens taken out of the key
+// registers (their bitmap byte per 8-token chunk) and handed on as explicit f32 entries.  The top-k lower bound stays valid: it is
+// taken over the unseen tokens, whose k-th largest value is a lower bound of the row's.  Rows with no entry left behind the bound take
+// nucleus_scan itself, i.e. the unpenalised sampler's token.
+template <int CH>
+__global__ __launch_bounds__(1024) void sample_token_pen_kernel(SampleArgsPen pa) {
+    __shared__ SampleLdsPen L;
+    const SampleArgs &a = pa.s;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    sample_prefetch(L, a, b, tid);
+    const bf16_t *row = a.logits + (int64_t)b * a.ld;
+    const uint16_t *row16 = reinterpret_cast<const uint16_t *>(row);
+    const int nchunk = a.V / 8;
+    unsigned char *srow = pa.seen + (int64_t)b * pa.rb;
+    uint32_t *shdr = reinterpret_cast<uint32_t *>(srow), *slist = shdr + 4, *sbm = slist + pa.cap;
+    uint32_t *uk = sbm + (a.V + 31) / 32, *ut = uk + pa.cap, *sk = ut + pa.cap, *stk = sk + pa.cap;
+    unsigned long long *em = reinterpret_cast<unsigned long long *>(srow + seen_em_offset(a.V, pa.cap));
+    const uint32_t nseen = pa.pen_on ? min((uint32_t)__builtin_amdgcn_readfirstlane((int)shdr[0]), (uint32_t)pa.cap) : 0u;
+    uint32_t w[CH][4];
+    sample_load<CH>(w, row, tid, nchunk);
+    uint32_t mb[(CH + 3) / 4] = {};             // the bitmap bytes of the thread's chunks, four per word
+    if (nseen) {
+        const unsigned char *bm8 = reinterpret_cast<const unsigned char *>(sbm);
+#pragma unroll
+        for (int k = 0; k < CH; ++k) {
+            const int c = tid + k * 1024;
+            if (c < nchunk) mb[k >> 2] |= (uint32_t)bm8[c] << (8 * (k & 3));
+        }
+    }
+    if (!a.greedy) {
+#pragma unroll
+        for (int i = 0; i < SAMPLE_BPT; ++i) L.cnt[i * 1024 + tid] = 0;
+    }
+    if (tid == 0) { L.tail = 0; L.d = 0; L.tok = 0; L.dk = 0xffffffffu; L.Zk = 0; L.klo = 0; L.ns = 0; L.ekmax = 0; L.emax = 0; }
+    for (int i = tid; i < SAMPLE_TM_BINS + 1; i += 1024) L.tmh[i] = 0;
+    __syncthreads();                            // the entry maxima below are atomics on the fields just zeroed
+    // the entries' largest key (sampling: the softmax shift) / the largest (key, lowest token) pair (greedy)
+    for (uint32_t j = tid; j < nseen; j += 1024) {
+        const uint32_t t = slist[j];
+        const uint32_t kk = pen_k32(row16[t], pa.pen);
+        if (a.greedy) atomicMax(&L.emax, ((unsigned long long)kk << 32) | (0xffffffffu - t));
+        else atomicMax(&L.ekmax, kk);
+    }
+    reg_fence<CH>(w);
+    const uint32_t kmaxi = sample_keys<CH, true>(w, tid, nchunk, mb);
+    const uint32_t kmax = sample_kmax(L, kmaxi, lane, wave);      // of the unseen tokens (0: none); its barrier also covers the maxima
+    const uint32_t ekmax = __builtin_amdgcn_readfirstlane(L.ekmax);
+    float m = scaled(kmax, a.inv_temp);
+    if (ekmax && (kmax == 0u || ekmax > k32_of_key(kmax))) m = fminf(fmaxf(f_of_k32(ekmax) * a.inv_temp, -3.0e38f), 3.0e38f);
+    uint32_t k2 = kmax, rank = 0;
+    bool use_regs = kmax != 0u;
+    unsigned long long emax = 0;
+    if (a.greedy) {
+        emax = uniform64(L.emax);
+        const uint32_t ek = (uint32_t)(emax >> 32);
+        if (ek && (kmax == 0u || ek > k32_of_key(kmax))) { use_regs = false; if (tid == 0) L.tok = 0xffffffffu - (uint32_t)emax; }
+    } else {
+        const uint32_t klo = sample_klo(L, a, tid, lane, wave, kmax, kmaxi);
+        sample_hist<CH>(L, a, w, kmax, klo, m);
+        // the entries: below the bound -> cut by top-k; below the window -> the tail mass; the rest -> the list, sorted below
+        for (uint32_t j = tid; j < nseen; j += 1024) {
+            const uint32_t t = slist[j];
+            const uint32_t kk = pen_k32(row16[t], pa.pen), top = kk >> 16;
+            if (klo && top < klo) continue;
+            if (kmax && top < kmax && kmax - top >= (uint32_t)SAMPLE_W) {
+                const unsigned long long q = mass_k32(kk, a.inv_temp, m);
+                if (q) atomicAdd(&L.tail, q);
+                continue;
+            }
+            const uint32_t i = atomicAdd(&L.ns, 1u);
+            uk[i] = kk;
+            ut[i] = t;
+        }
+        __syncthreads();
+        const uint32_t ns = __builtin_amdgcn_readfirstlane(L.ns);
+        if (ns == 0u) {
+            if (kmax) nucleus_scan(L, a, b, tid, lane, wave, kmax, klo, m, k2, rank);
+        } else {
+            // rank of every entry: key descending, token ascending among equal keys (tokens are distinct)
+            for (uint32_t i = tid; i < ns; i += 1024) {
+                const uint32_t ki = uk[i], ti = ut[i];
+                uint32_t r = 0;
+                for (uint32_t j = 0; j < ns; ++j) {
+                    const uint32_t kj = uk[j];
+                    r += (kj > ki || (kj == ki && ut[j] < ti)) ? 1u : 0u;
+                }
+                sk[r] = ki;
+                stk[r] = ti;
+            }
+            __syncthreads();
+            // exclusive prefix masses em[0..ns]: contiguous segments per thread
+            const uint32_t seg = (ns + 1023) / 1024, s0 = min(ns, tid * seg), s1 = min(ns, s0 + seg);
+            unsigned long long ls = 0;
+            for (uint32_t i = s0; i < s1; ++i) ls += mass_k32(sk[i], a.inv_temp, m);
+            unsigned long long inc = ls;
+#pragma unroll
+            for (int dd = 1; dd < 64; dd <<= 1) {
+                const unsigned long long o = __shfl_up(inc, dd, 64);
+                if (lane >= dd) inc += o;
+            }
+            if (lane == 63) L.wsum[wave] = inc;
+            __syncthreads();
+            unsigned long long acc = 0;
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                if (i < wave) acc += L.wsum[i];
+            acc += inc - ls;
+            for (uint32_t i = s0; i < s1; ++i) { em[i] = acc; acc += mass_k32(sk[i], a.inv_temp, m); }
+            if (s1 == ns && s0 < s1) em[ns] = acc;
+            __syncthreads();
+            uint32_t eidx;
+            nucleus_scan_pen(L, a, b, tid, lane, wave, kmax, klo, m, ns, sk, em, k2, rank, eidx);
+            if (eidx != 0xffffffffu) {
+                use_regs = false;
+                if (tid == 0) L.tok = stk[eidx];
+            }
+        }
+    }
+    // ---- the rank-th unseen token whose key is k2 (greedy: the lowest index holding the maximum)
+    if (use_regs) {
+        sample_pick<CH>(L, a, w, tid, lane, wave, k2, rank);
+        // greedy, an entry tied with the unseen maximum: the lower of the two indices (thread 0 wrote L.tok)
+        if (a.greedy && tid == 0 && emax && (uint32_t)(emax >> 32) == k32_of_key(kmax)) L.tok = min(L.tok, 0xffffffffu - (uint32_t)emax);
+    }
+    sample_finish(L, a, b, tid);
+    // the emitted token joins the row's set (HF appends it, pad included, to input_ids)
+    if (tid == 0) {
+        const long long nxt = L.done ? a.pad : (long long)L.tok;
+        if (nxt >= 0 && nxt < a.V) {
+            const uint32_t bit = 1u << (nxt & 31), old = sbm[nxt >> 5], cnt = shdr[0];
+            if (!(old & bit) && cnt < (uint32_t)pa.cap) {
+                sbm[nxt >> 5] = old | bit;
+                slist[cnt] = (uint32_t)nxt;
+                shdr[0] = cnt + 1u;
+            }
+        }
+    }
 }
 
 }  // namespace ll
@@ -663,6 +1050,50 @@ extern "C" int ll_sample_token_topk_ws_bf16(const void *logits, int64_t ld, int 
     else if (per <= 16) hipLaunchKernelGGL((sample_token_kernel<16>), dim3(B), dim3(1024), 0, s, a);
     else if (per <= 19) hipLaunchKernelGGL((sample_token_kernel<19>), dim3(B), dim3(1024), 0, s, a);     // 152 064 (Qwen2): 76 key registers
     else hipLaunchKernelGGL((sample_token_kernel<20>), dim3(B), dim3(1024), 0, s, a);
+    LL_LAUNCH_CHECK();
+    return LL_OK;
+}
+
+extern "C" int64_t ll_seen_set_bytes(int B, int V, int cap) { return (B <= 0 || V <= 0 || cap < 0) ? 0 : (int64_t)B * seen_row_bytes(V, cap); }
+
+extern "C" int ll_seen_set_init(void *seen, int64_t seen_bytes, int B, int V, int cap, const int64_t *input_ids, int64_t ld, int P, void *stream) {
+    LL_CHECK(seen && B >= 1 && V >= 1 && cap >= 1 && P >= 0 && (P == 0 || (input_ids && ld >= P)), "ll_seen_set_init: bad argument");
+    LL_CHECK(seen_bytes >= ll_seen_set_bytes(B, V, cap) && ((uintptr_t)seen & 15) == 0,
+             "ll_seen_set_init: set of %lld bytes, need %lld (16-byte aligned)", (long long)seen_bytes, (long long)ll_seen_set_bytes(B, V, cap));
+    hipLaunchKernelGGL(seen_init_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, (unsigned char *)seen, seen_row_bytes(V, cap), V, cap,
+                       (const long long *)input_ids, ld, P);
+    LL_LAUNCH_CHECK();
+    return LL_OK;
+}
+
+extern "C" int ll_sample_token_penalty_bf16(const void *logits, int64_t ld, int B, int V, float inv_temp, float top_p, int top_k, int greedy,
+                                            const int64_t *seed, const int64_t *eos, int n_eos, int64_t pad, void *done, int64_t *tok,
+                                            int64_t *out_tokens, int64_t ld_out, int max_new, int64_t *step, int64_t *posid, int64_t *pos,
+                                            int advance, void *seen, int64_t seen_bytes, int cap, float penalty, void *stream) {
+    LL_CHECK(logits && seed && done && tok && out_tokens && step && (n_eos == 0 || eos) && seen, "ll_sample_token_penalty_bf16: null argument");
+    LL_CHECK(B >= 1 && V >= 8 && V % 8 == 0 && V <= 1024 * 8 * 20 && ld % 8 == 0,
+             "ll_sample_token_penalty_bf16: vocabulary %d must be a multiple of 8 and <= 163840", V);
+    LL_CHECK(greedy || (inv_temp > 0.f && top_p >= 0.f), "ll_sample_token_penalty_bf16: temperature and top_p must be positive");
+    LL_CHECK(penalty > 0.f, "ll_sample_token_penalty_bf16: the penalty must be a positive float");
+    LL_CHECK(cap >= 1 && seen_bytes >= ll_seen_set_bytes(B, V, cap) && ((uintptr_t)seen & 15) == 0,
+             "ll_sample_token_penalty_bf16: set of %lld bytes, need %lld (16-byte aligned)", (long long)seen_bytes,
+             (long long)ll_seen_set_bytes(B, V, cap));
+    SampleArgsPen pa;
+    SampleArgs &a = pa.s;
+    a.logits = (const bf16_t *)logits; a.ld = ld; a.V = V; a.inv_temp = inv_temp; a.top_p = top_p; a.top_k = top_k < 0 ? 0 : top_k; a.greedy = greedy;
+    a.seed = (const long long *)seed; a.eos = (const long long *)eos; a.n_eos = n_eos; a.pad = pad;
+    a.done = (unsigned char *)done; a.tok = (long long *)tok; a.out_tokens = (long long *)out_tokens; a.ld_out = ld_out;
+    a.max_new = max_new; a.step = (long long *)step; a.posid = (long long *)posid; a.pos = (long long *)pos;
+    a.advance = advance; a.dbg = nullptr;
+    a.cand_total = nullptr; a.cand = nullptr;           // no split path: its candidates are picked on raw keys
+    pa.seen = (unsigned char *)seen; pa.rb = seen_row_bytes(V, cap); pa.cap = cap; pa.pen = penalty; pa.pen_on = penalty != 1.f;
+    hipStream_t s = (hipStream_t)stream;
+    const int per = cdiv(V, 8 * 1024);
+    if (per <= 2) hipLaunchKernelGGL((sample_token_pen_kernel<2>), dim3(B), dim3(1024), 0, s, pa);
+    else if (per <= 8) hipLaunchKernelGGL((sample_token_pen_kernel<8>), dim3(B), dim3(1024), 0, s, pa);
+    else if (per <= 16) hipLaunchKernelGGL((sample_token_pen_kernel<16>), dim3(B), dim3(1024), 0, s, pa);
+    else if (per <= 19) hipLaunchKernelGGL((sample_token_pen_kernel<19>), dim3(B), dim3(1024), 0, s, pa);
+    else hipLaunchKernelGGL((sample_token_pen_kernel<20>), dim3(B), dim3(1024), 0, s, pa);
     LL_LAUNCH_CHECK();
     return LL_OK;
 }

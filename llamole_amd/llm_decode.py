@@ -21,8 +21,33 @@ import os
 import torch
 
 
-def sample_top_p(logits: torch.Tensor, temperature: float, top_p: float, generator=None, top_k: Optional[int] = None) -> torch.Tensor:
-    """HF TemperatureLogitsWarper + TopKLogitsWarper + TopPLogitsWarper + multinomial, without host syncs.  logits [B,V] float."""
+def check_repetition_penalty(p) -> Optional[float]:
+    """HF generate's handling: None or 1.0 (an int 1 included) = off, no processor; anything else goes to RepetitionPenaltyLogitsProcessor,
+    which takes a strictly positive Python float only (an int such as 2 raises ValueError, as it does there)."""
+    if p is None or (not isinstance(p, (bool, str)) and isinstance(p, (int, float)) and p == 1.0):
+        return None
+    if not isinstance(p, float) or not (p > 0):
+        raise ValueError(f"`penalty` has to be a strictly positive float, but is {p}")
+    return float(p)
+
+
+def apply_repetition_penalty(logits: torch.Tensor, ids: torch.Tensor, penalty: float) -> torch.Tensor:
+    """HF RepetitionPenaltyLogitsProcessor on a float32 copy of ``logits`` [B,V]: every token of ``ids`` [B,L] (duplicates harmless)
+    gets x < 0 ? x * penalty : x / penalty."""
+    logits = logits.float().clone()
+    if ids.shape[1] == 0:
+        return logits
+    s = torch.gather(logits, 1, ids)
+    s = torch.where(s < 0, s * penalty, s / penalty)
+    return logits.scatter_(1, ids, s)
+
+
+def sample_top_p(logits: torch.Tensor, temperature: float, top_p: float, generator=None, top_k: Optional[int] = None,
+                 repetition_penalty: Optional[float] = None, penalty_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """HF TemperatureLogitsWarper + TopKLogitsWarper + TopPLogitsWarper + multinomial, without host syncs.  logits [B,V] float.
+    With ``repetition_penalty`` and ``penalty_ids`` [B,L], HF's RepetitionPenaltyLogitsProcessor runs first."""
+    if repetition_penalty is not None and repetition_penalty != 1.0 and penalty_ids is not None:
+        logits = apply_repetition_penalty(logits, penalty_ids, repetition_penalty)
     logits = logits.float()
     logits = torch.nan_to_num(logits, nan=0.0, posinf=torch.finfo(torch.float32).max, neginf=torch.finfo(torch.float32).min)
     if temperature is not None and temperature != 1.0:
@@ -119,6 +144,7 @@ class GraphedDecoder:
         self.eos_buf = torch.full((N_EOS_SLOTS,), -1, dtype=torch.long, device=device)
         self.logits = None
         self.sample_ws = None
+        self.seen = None                # per-row set of seen tokens of the repetition penalty (ll_seen_set_*), allocated on first use
         self._graph = None
         self._cache_fused = False
         self._side_graphs = {}          # captured against the buffers above
@@ -212,9 +238,19 @@ class GraphedDecoder:
         """One launch: sample (or argmax) from bf16 logits [B,V], write tok / out_buf[:, step], update done / step and,
         with ``advance``, the position counters the next forward reads."""
         from . import _lib
-        greedy, inv_temp, top_p, pad, top_k = sp
+        greedy, inv_temp, top_p, pad, top_k, penalty = sp
         B, V = logits.shape
         lib = _lib.load()
+        if penalty != 1.0:
+            rc = lib.ll_sample_token_penalty_bf16(logits.data_ptr(), logits.stride(0), B, V, inv_temp, top_p, int(top_k), int(greedy),
+                                                  self.seed_buf.data_ptr(), self.eos_buf.data_ptr(), N_EOS_SLOTS, pad,
+                                                  self.done.data_ptr(), self.tok.data_ptr(), self.out_buf.data_ptr(),
+                                                  self.out_buf.stride(0), self.out_buf.shape[1], self.stepc.data_ptr(),
+                                                  self.posid.data_ptr(), self.pos.data_ptr(), advance, self.seen.data_ptr(), self.seen.numel(),
+                                                  self.seen_cap, penalty, torch.cuda.current_stream().cuda_stream)
+            if rc != 0:
+                _lib.check(rc, "ll_sample_token_penalty_bf16")
+            return
         if self.sample_ws is None or self.sample_ws.device != logits.device:
             # workspace of the split top-k sampler (candidate lists; zero-filled once, the sampler leaves it clean): a static buffer of the graph
             self.sample_ws = torch.zeros(int(lib.ll_sample_workspace_bytes(B)), dtype=torch.uint8, device=logits.device)
@@ -228,8 +264,24 @@ class GraphedDecoder:
         if rc != 0:
             _lib.check(rc, "ll_sample_token_topk_ws_bf16")
 
-    def _generate_hip(self, logits, sp, P, plen, eos_list, max_new_tokens, generator, device):
+    def _generate_hip(self, logits, sp, P, plen, eos_list, max_new_tokens, generator, device, penalty_ids=None):
         """Decode loop with the fused sampler: per token the host only replays ONE graph (forward + sampler)."""
+        if sp[5] != 1.0:
+            # the repetition penalty's set of seen tokens: a static buffer of the captured step, reseeded here by one launch
+            from . import _lib
+            lib = _lib.load()
+            B, V = logits.shape
+            cap = self.out_buf.shape[1]             # the static-cache length >= prompt + new tokens
+            if self.seen is None or self.seen_cap != cap or self.seen_V != V:
+                self.seen = torch.empty(int(lib.ll_seen_set_bytes(B, V, cap)), dtype=torch.uint8, device=device)
+                self.seen_cap, self.seen_V = cap, V
+                self._graph = None
+            ids = penalty_ids if penalty_ids is not None else torch.zeros(B, 0, dtype=torch.long, device=device)
+            ids = ids.contiguous()
+            rc = lib.ll_seen_set_init(self.seen.data_ptr(), self.seen.numel(), B, V, cap, ids.data_ptr() if ids.numel() else None,
+                                      max(1, ids.shape[1]), ids.shape[1], torch.cuda.current_stream().cuda_stream)
+            if rc != 0:
+                _lib.check(rc, "ll_seen_set_init")
         self.done.zero_()
         self.stepc.zero_()
         self.out_buf.fill_(sp[3])
@@ -278,7 +330,12 @@ class GraphedDecoder:
     def generate(self, input_ids: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
                  inputs_embeds: Optional[torch.Tensor] = None, max_new_tokens: int = 128, do_sample: bool = True,
                  temperature: float = 1.0, top_p: float = 1.0, eos_token_id: Optional[Sequence[int]] = None,
-                 pad_token_id: Optional[int] = None, generator=None, top_k: Optional[int] = None, **other) -> torch.Tensor:
+                 pad_token_id: Optional[int] = None, generator=None, top_k: Optional[int] = None,
+                 repetition_penalty: Optional[float] = None, **other) -> torch.Tensor:
+        # HF RepetitionPenaltyLogitsProcessor: every token of the call's input_ids (prompt, pads included, then each generated token;
+        # an inputs_embeds call starts from none) gets x < 0 ? x * p : x / p ahead of the sampling options below
+        penalty = check_repetition_penalty(repetition_penalty)
+        penalty = 1.0 if penalty is None else penalty
         _reject_unsupported_generation_options(other)
         from ._trace import mark
         mark("generate: enter")
@@ -327,8 +384,9 @@ class GraphedDecoder:
                 and (not do_sample or (temperature or 1.0) > 0)):
             import numpy as np
             temp = 1.0 if temperature is None else float(temperature)
-            sp = (not do_sample, float(np.float32(1.0) / np.float32(temp)), 1.0 if top_p is None else float(top_p), int(pad), top_k)
-            new_tokens = self._generate_hip(logits, sp, P, plen, eos.tolist(), max_new_tokens, generator, device)
+            sp = (not do_sample, float(np.float32(1.0) / np.float32(temp)), 1.0 if top_p is None else float(top_p), int(pad), top_k,
+                  float(np.float32(penalty)))
+            new_tokens = self._generate_hip(logits, sp, P, plen, eos.tolist(), max_new_tokens, generator, device, input_ids)
             mark("generate: decode loop done")
             return torch.cat([input_ids, new_tokens], dim=1) if input_ids is not None else new_tokens
         if self._sample_key is not None:     # a graph captured with the fused sampler does not fit the torch-sampler loop
@@ -338,10 +396,19 @@ class GraphedDecoder:
         done = torch.zeros(B, dtype=torch.bool, device=device)
         self.posid.copy_(plen)                                           # position id of the next token, per row
         n_done_steps = 0
+        seen = None
+        if penalty != 1.0:
+            seen = input_ids if input_ids is not None else torch.zeros(B, 0, dtype=torch.long, device=device)
         for t in range(max_new_tokens):
-            nxt = sample_top_p(logits, temperature, top_p, generator, top_k) if do_sample else logits.argmax(dim=-1)
+            if seen is not None:
+                pl = apply_repetition_penalty(logits, seen, penalty)
+                nxt = sample_top_p(pl, temperature, top_p, generator, top_k) if do_sample else pl.argmax(dim=-1)
+            else:
+                nxt = sample_top_p(logits, temperature, top_p, generator, top_k) if do_sample else logits.argmax(dim=-1)
             nxt = torch.where(done, torch.full_like(nxt, pad), nxt)
             new_tokens[:, t] = nxt
+            if seen is not None:
+                seen = torch.cat([seen, nxt.view(B, 1)], dim=1)
             if eos.numel():
                 done = done | torch.isin(nxt, eos)
             n_done_steps = t + 1

@@ -1,5 +1,6 @@
 """Times ll_sample_token_topk_bf16 on one row of synthetic logits: with the dbg tap (counts the whole row) and without
-(top-k lower bound), and with the workspace (candidates launch + finish launch).  python tools/sample_time.py [V] [top_k] [B]"""
+(top-k lower bound), and with the workspace (candidates launch + finish launch).  python tools/sample_time.py [V] [top_k] [B] [seen]
+With [seen]: also ll_sample_token_penalty_bf16 (repetition_penalty 1.3 over `seen` tokens per row, and 1.0 = off) on the same rows."""
 import os
 import sys
 
@@ -60,3 +61,36 @@ for name, wd, k, gr in (("whole row (dbg tap)", True, top_k, 0), ("top-k bound",
         ref = toks
     elif name.startswith("top-k"):
         print("   tokens equal to the whole-row path:", bool((toks == ref).all()), "distinct tokens:", int(toks.unique().numel()))
+
+if len(sys.argv) > 4:
+    n_seen = int(sys.argv[4])
+    cap = max(1024, n_seen)
+    seen = torch.zeros(int(lib.ll_seen_set_bytes(B, V, cap)), dtype=torch.uint8, device=d)
+    # the seen tokens include each row's largest logits (a decode repeats what it found likely)
+    ids = torch.cat([logits.float().topk(min(8, n_seen), dim=-1).indices,
+                     torch.randint(0, V, (B, max(0, n_seen - 8)), generator=g).to(d)], dim=1).contiguous()
+
+    def run_pen(p, k, greedy):
+        rc = lib.ll_sample_token_penalty_bf16(logits.data_ptr(), logits.stride(0), B, V, 1.0 / 0.7, 0.9, k, greedy, seed.data_ptr(), eos.data_ptr(), 32, 0,
+                                              done.data_ptr(), tok.data_ptr(), out.data_ptr(), out.stride(0), out.shape[1], step.data_ptr(), None,
+                                              None, 0, seen.data_ptr(), seen.numel(), cap, p, st)
+        assert rc == 0
+
+    def timed_pen(p, k, greedy, iters=300):
+        # the set grows by the emitted token per launch, as in a decode; it is reseeded before the timed loop
+        for _ in range(20):
+            run_pen(p, k, greedy)
+        assert lib.ll_seen_set_init(seen.data_ptr(), seen.numel(), B, V, cap, ids.data_ptr(), ids.stride(0), ids.shape[1], st) == 0
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        step.zero_()
+        e0.record()
+        for _ in range(iters):
+            run_pen(p, k, greedy)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters * 1e3
+
+    assert lib.ll_seen_set_init(seen.data_ptr(), seen.numel(), B, V, cap, ids.data_ptr(), ids.stride(0), ids.shape[1], st) == 0
+    for name, p, k, gr in ((f"penalty 1.3, top-k", 1.3, top_k, 0), ("penalty 1.0, top-k", 1.0, top_k, 0), ("penalty 1.3, top_k off", 1.3, 0, 0),
+                           ("penalty 1.3, greedy", 1.3, 0, 1)):
+        print(f"{name:26s} {timed_pen(p, k, gr):7.2f} us per launch (one launch, B={B}, V={V}, {n_seen} seen tokens per row)")
