@@ -359,6 +359,29 @@ int ll_sample_token_penalty_bf16(const void *logits, int64_t ld, int B, int V, f
                                  int64_t *out_tokens, int64_t ld_out, int max_new, int64_t *step, int64_t *posid, int64_t *pos, int advance,
                                  void *seen, int64_t seen_bytes, int cap, float penalty, void *stream);
 
+/* Beam search of the graphed decode (HF GenerationMixin._beam_search; llamole_amd/llm_beam.py states the same step in torch and the
+ * layout of its state): B items of nb beams, rows r = b * nb + j.
+ * ll_beam_state_bytes(B, nb, K, T): bytes of the state (int32 / f32 segments: running scores, hypotheses, flags, parents, per-step
+ *     tokens and parents of T steps, the row candidates); K = max(2, 1 + n_eos) * nb.
+ * ll_beam_step_bf16 : one step in two launches, no host sync.  logits bf16 [B*nb, V] (row stride ld, V % 8 == 0, V <= 163840);
+ *     2 <= nb <= 16, K <= 512, nb * K <= 4096, n_eos <= 32; early_stopping 0 = False, 1 = True, 2 = "never".  do_sample = beam sample:
+ *     HF's Temperature (inv_temp = 1 / temperature), TopK and TopP warpers on the log-probs with min_tokens_to_keep = n_eos + 1
+ *     (1 <= top_k, max(top_k, n_eos + 1) <= 512), then K draws without replacement (Gumbel-top-K, Philox4x32-10 keyed by *seed and
+ *     counter (token, row, step)).  Writes tok[r] (the next input), the parents (state) and, with advance, posid[r] += 1 and
+ *     pos[0] += 1.  A step after the global stop changes nothing.  Ties: the higher score, then the lower flat index beam * V + token.
+ * ll_beam_kv_reorder_bf16 : one launch over all layers: kv_ptrs[n_tensors] (device) point at the StaticCache tensors [B*nb, nkv,
+ *     maxlen, D] bf16; slots [*first, *pos) of row r take those of row par[r] (the state's parents; items whose parents are the
+ *     identity move nothing), or with from_first_beam those of the item's beam 0.  first and pos are device int64 counters, read by
+ *     the kernel.  In place; D % 8 == 0, nb * D <= 16384, n_tensors * B * nkv <= 65535.
+ *     Beam sample keeps at most 1024 survivors per row: when more tokens tie at the top-k threshold value, the lowest-indexed ones;
+ *     at the nucleus boundary the lower-indexed of equal tokens is removed first (HF's ascending sort taken stably). */
+int64_t ll_beam_state_bytes(int B, int nb, int K, int T);
+int ll_beam_step_bf16(const void *logits, int64_t ld, int B, int nb, int V, int K, int T, void *state, int64_t state_bytes,
+                      const int64_t *eos, int n_eos, int max_new, float length_penalty, int early_stopping, int do_sample, float inv_temp,
+                      int top_k, float top_p, const int64_t *seed, int64_t *tok, int64_t *posid, int64_t *pos, int advance, void *stream);
+int ll_beam_kv_reorder_bf16(const int64_t *kv_ptrs, int n_tensors, int B, int nb, int nkv, int maxlen, int D, const int *par,
+                            const int64_t *first, int from_first_beam, const int64_t *pos, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

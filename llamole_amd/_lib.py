@@ -100,6 +100,9 @@ SIGNATURES = {
     "ll_seen_set_init": (_I, [_P, _I64, _I, _I, _I, _P, _I64, _I, _P]),
     "ll_sample_token_penalty_bf16": (_I, [_P, _I64, _I, _I, _F, _F, _I, _I, _P, _P, _I, _I64, _P, _P, _P, _I64, _I, _P, _P, _P, _I,
                                           _P, _I64, _I, _F, _P]),
+    "ll_beam_state_bytes": (_I64, [_I, _I, _I, _I]),
+    "ll_beam_step_bf16": (_I, [_P, _I64, _I, _I, _I, _I, _I, _P, _I64, _P, _I, _I, _F, _I, _I, _F, _I, _F, _P, _P, _P, _P, _I, _P]),
+    "ll_beam_kv_reorder_bf16": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
 }
 
 # include/llamole_hip_tuning.h: exported by libllamole_hip_tuning.so only (the LL_TUNING=1 build of the same sources)

@@ -93,8 +93,25 @@ def _reject_unsupported_generation_options(other: dict) -> None:
                                   f"use the HF path (llm_decode='hf')")
 
 
+def check_beam_options(num_beams, early_stopping):
+    """HF GenerationConfig's validation of the beam options: num_beams a positive int, early_stopping one of False, True, "never"
+    (None = HF's default False).  Returns (num_beams, early_stopping)."""
+    import numbers
+    if isinstance(num_beams, bool) or not isinstance(num_beams, numbers.Integral) or num_beams < 1:
+        raise ValueError(f"`num_beams` has to be a strictly positive integer, but is {num_beams}")
+    if early_stopping is None:
+        early_stopping = False
+    if not (early_stopping is True or early_stopping is False or early_stopping == "never"):
+        raise ValueError(f"`early_stopping` must be a boolean or 'never', but is {early_stopping}.")
+    return int(num_beams), early_stopping
+
+
 MAX_HIP_VOCAB = 163840   # ll_sample_token_bf16 keeps a whole row of logits in one workgroup's registers
 N_EOS_SLOTS = 32
+# bounds of the HIP beam step (ll_beam_step_bf16): beams per item, K = max(2, 1 + n_eos) * nb continuations kept per item, nb * K
+# (the item's merge sorts them in LDS), and the top-k of beam sample (its survivors are sorted in LDS); outside them the torch step
+# runs, with the same results
+MAX_HIP_BEAMS, MAX_HIP_BEAM_K, MAX_HIP_BEAM_NK, MAX_HIP_BEAM_TOPK = 16, 512, 4096, 512
 
 
 class GraphedDecoder:
@@ -145,6 +162,8 @@ class GraphedDecoder:
         self.logits = None
         self.sample_ws = None
         self.seen = None                # per-row set of seen tokens of the repetition penalty (ll_seen_set_*), allocated on first use
+        self._beam_key = None           # beam search: state buffer (llm_beam.py) and the captured forward + beam step
+        self._beam_graph = None
         self._graph = None
         self._cache_fused = False
         self._side_graphs = {}          # captured against the buffers above
@@ -208,6 +227,8 @@ class GraphedDecoder:
         info = self._last
         if info is None:
             raise RuntimeError("continue_hidden needs a preceding generate() on this decoder")
+        if info.get("beams", 1) > 1:
+            raise RuntimeError("continue_hidden after a beam search: the cache holds the running beams, not the returned sequences")
         B, S = tail_ids.shape
         P = info["P"]
         if start < P or start + S > self.mask.shape[1]:
@@ -331,11 +352,24 @@ class GraphedDecoder:
                  inputs_embeds: Optional[torch.Tensor] = None, max_new_tokens: int = 128, do_sample: bool = True,
                  temperature: float = 1.0, top_p: float = 1.0, eos_token_id: Optional[Sequence[int]] = None,
                  pad_token_id: Optional[int] = None, generator=None, top_k: Optional[int] = None,
-                 repetition_penalty: Optional[float] = None, **other) -> torch.Tensor:
+                 repetition_penalty: Optional[float] = None, num_beams: Optional[int] = None, length_penalty: Optional[float] = None,
+                 early_stopping=None, **other) -> torch.Tensor:
         # HF RepetitionPenaltyLogitsProcessor: every token of the call's input_ids (prompt, pads included, then each generated token;
         # an inputs_embeds call starts from none) gets x < 0 ? x * p : x / p ahead of the sampling options below
         penalty = check_repetition_penalty(repetition_penalty)
         penalty = 1.0 if penalty is None else penalty
+        if num_beams is not None and (isinstance(num_beams, bool) or num_beams != 1):
+            nb, es = check_beam_options(num_beams, early_stopping)
+            if penalty != 1.0:
+                raise NotImplementedError("GraphedDecoder.generate does not implement repetition_penalty together with num_beams > 1")
+            _reject_unsupported_generation_options(other)
+            return self._generate_beam(input_ids, attention_mask, inputs_embeds, max_new_tokens, bool(do_sample), temperature, top_p,
+                                       eos_token_id, pad_token_id, generator, int(top_k) if top_k else 0, nb,
+                                       1.0 if length_penalty is None else float(length_penalty), es)
+        # no beam search: the beam options go through the same check as before (a non-neutral one raises there)
+        for k, v in (("num_beams", num_beams), ("length_penalty", length_penalty), ("early_stopping", early_stopping)):
+            if v is not None:
+                other[k] = v
         _reject_unsupported_generation_options(other)
         from ._trace import mark
         mark("generate: enter")
@@ -446,3 +480,172 @@ class GraphedDecoder:
         if input_ids is not None:
             return torch.cat([input_ids, new_tokens], dim=1)
         return new_tokens
+
+    # ------------------------------------------------------------------ beam search (num_beams > 1)
+    def _beam_hip_ok(self, logits: torch.Tensor, p) -> bool:
+        """The HIP beam step's bounds (ll_beam_step_bf16); elsewhere the torch step runs."""
+        V = logits.shape[1]
+        return (self.sampler == "hip" and logits.is_cuda and logits.dtype == torch.bfloat16 and V % 8 == 0 and V <= MAX_HIP_VOCAB
+                and logits.stride(1) == 1 and logits.stride(0) % 8 == 0 and p.eos.numel() <= N_EOS_SLOTS and p.nb <= MAX_HIP_BEAMS
+                and p.K <= MAX_HIP_BEAM_K and p.nb * p.K <= MAX_HIP_BEAM_NK
+                and (not p.do_sample or ((p.temperature or 1.0) > 0 and 1 <= p.top_k and max(p.top_k, p.min_keep) <= MAX_HIP_BEAM_TOPK)))
+
+    def _kv_table(self, B: int, nb: int):
+        """Device table of the StaticCache K / V tensors ([B*nb, nkv, maxlen, D] bf16 each) for ll_beam_kv_reorder_bf16, or None outside
+        the kernel's bounds (D % 8 == 0, nb * D <= 16384, tensors * B * nkv <= 65535)."""
+        R = B * nb
+        ts = []
+        for layer in self.cache.layers:
+            ts += [getattr(layer, "keys", None), getattr(layer, "values", None)]
+        if not ts or any(x is None or not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 4 or not x.is_contiguous()
+                         or x.shape != ts[0].shape or x.shape[0] != R for x in ts):
+            return None
+        nkv, D = ts[0].shape[1], ts[0].shape[3]
+        if D % 8 != 0 or nb * D > 16384 or len(ts) * B * nkv > 65535:
+            return None
+        ptrs = tuple(x.data_ptr() for x in ts)
+        if getattr(self, "_kv_ptrs_key", None) != ptrs:
+            self._kv_ptrs_key = ptrs
+            self._kv_ptrs = torch.tensor(ptrs, dtype=torch.int64, device=ts[0].device)
+        return self._kv_ptrs, len(ts), tuple(ts[0].shape)
+
+    def _hip_beam(self, logits: torch.Tensor, p, advance: int, step0: bool):
+        """Two launches of the beam step (candidates per row, then the merge per item) and one of the KV reorder.  Step 0: every row
+        takes beam 0's slots [0, pos) (the prompt); later steps: slots [P, pos) of every layer follow the step's parents, with P read
+        from the device counter ``beam_first`` (set per call: a captured step serves every prompt length of its bucket)."""
+        import numpy as np
+        from . import _lib
+        lib = _lib.load()
+        V = logits.shape[1]
+        stream = torch.cuda.current_stream().cuda_stream
+        es = 2 if p.early_stopping == "never" else int(p.early_stopping is True)
+        temp = 1.0 if p.temperature is None else float(p.temperature)
+        rc = lib.ll_beam_step_bf16(logits.data_ptr(), logits.stride(0), p.B, p.nb, V, p.K, p.T, self.beam_buf.data_ptr(), self.beam_buf.numel(),
+                                   self.eos_buf.data_ptr(), int(p.eos.numel()), p.max_new, float(p.length_penalty), es, int(p.do_sample),
+                                   float(np.float32(1.0) / np.float32(temp)), int(p.top_k), float(p.top_p), self.seed_buf.data_ptr(),
+                                   self.tok.data_ptr(), self.posid.data_ptr(), self.pos.data_ptr(), advance, stream)
+        if rc != 0:
+            _lib.check(rc, "ll_beam_step_bf16")
+        ptrs, n, (R, nkv, maxlen, D) = self._kv
+        first = self.beam_first[1:] if step0 else self.beam_first[:1]
+        rc = lib.ll_beam_kv_reorder_bf16(ptrs.data_ptr(), n, p.B, p.nb, nkv, maxlen, D, self._beam_state.par.data_ptr(), first.data_ptr(),
+                                         int(step0), self.pos.data_ptr(), stream)
+        if rc != 0:
+            _lib.check(rc, "ll_beam_kv_reorder_bf16")
+
+    def _generate_beam(self, input_ids, attention_mask, inputs_embeds, max_new_tokens, do_sample, temperature, top_p, eos_token_id,
+                       pad_token_id, generator, top_k, nb, length_penalty, early_stopping):
+        """HF beam search / beam sample (llm_beam.py) over the B prompts expanded to B*nb rows: per token one captured step = forward
+        + beam step + KV reorder.  Returns the best hypothesis of each item, prompt first for an input_ids call (HF's output)."""
+        from ._trace import mark
+        from .llm_accel import refresh_weight_copies
+        from .llm_beam import BeamParams, BeamState, beam_step_torch, beams_to_keep, finalize, reorder_cache_torch, state_layout
+        mark("generate: enter")
+        refresh_weight_copies(self.model)
+        ref = input_ids if input_ids is not None else inputs_embeds
+        B, P = ref.shape[0], ref.shape[1]
+        device = ref.device
+        if attention_mask is None:
+            attention_mask = torch.ones(B, P, dtype=torch.long, device=device)
+        R = B * nb
+
+        def ex(x):
+            return None if x is None else x.repeat_interleave(nb, dim=0)
+        ids_x, mask_x, emb_x = ex(input_ids), ex(attention_mask), ex(inputs_embeds)
+        max_len = -(-(P + max_new_tokens) // self.len_bucket) * self.len_bucket
+        self._prepare(R, max_len, device, inputs_embeds is not None)
+        self._last = None
+        eos = torch.tensor(list(eos_token_id) if isinstance(eos_token_id, (list, tuple)) else
+                           ([] if eos_token_id is None else [eos_token_id]), dtype=torch.long, device=device)
+        pad = pad_token_id if pad_token_id is not None else (int(eos[0]) if eos.numel() else 0)
+        fill = (int(pad) if pad else int(eos[0])) if eos.numel() else -1      # HF: pad_token_id or eos[0]
+        # ---- prefill of all B*nb rows (HF's expanded input), then every row's prompt slots are made beam 0's by the step-0 reorder
+        self.mask.fill_(1)
+        self.mask[:, :P] = mask_x
+        plen = mask_x.long().sum(dim=1, keepdim=True)
+        pos_ids = (mask_x.long().cumsum(dim=1) - 1).clamp_min(0)
+        kw = dict(inputs_embeds=emb_x) if emb_x is not None else dict(input_ids=ids_x)
+        pre = dict(attention_mask=self.mask[:, :P], past_key_values=self.cache, cache_position=torch.arange(P, device=device),
+                   position_ids=pos_ids, use_cache=True, return_dict=True, **kw)
+        try:
+            out = self.model(logits_to_keep=1, **pre)
+        except TypeError:
+            out = self.model(**pre)
+        logits = out.logits[:, -1, :]
+        mark("generate: prefill enqueued")
+        for layer in self.cache.layers:
+            if hasattr(layer, "cumulative_length"):
+                layer.cumulative_length.fill_(P)
+        # the cache ends up holding running beams, not the returned sequences: continue_hidden refuses after a beam call
+        self._last = dict(P=P, plen=plen, max_new=max_new_tokens, from_ids=input_ids is not None, beams=nb)
+        if self.fused_cache and not self._cache_fused and device.type == "cuda":
+            from .llm_accel import fuse_cache_update
+            self._cache_fused = fuse_cache_update(self.cache) > 0
+        K = beams_to_keep(nb, eos.numel())
+        p = BeamParams(B, nb, K, max_len, max_new_tokens, eos, length_penalty, early_stopping, do_sample, temperature, top_k,
+                       1.0 if top_p is None else float(top_p))
+        skey = (B, nb, K, max_len)
+        if getattr(self, "_beam_key", None) != skey or self.beam_buf.device != device:
+            self._beam_key = skey
+            self.beam_buf = torch.zeros(state_layout(B, nb, K, max_len)[1], dtype=torch.uint8, device=device)
+            self.beam_first = torch.zeros(2, dtype=torch.int64, device=device)    # [P of the call, 0]: first slot the reorder moves
+            self._beam_graph = None
+        st = self._beam_state = BeamState(self.beam_buf, B, nb, K, max_len)
+        st.reset()
+        self._kv = self._kv_table(B, nb) if self._beam_hip_ok(logits, p) else None
+        hip = self._kv is not None
+        self.posid.copy_(plen)
+        self.pos.fill_(P)
+        if hip:
+            self.eos_buf.fill_(-1)
+            if eos.numel():
+                self.eos_buf[:eos.numel()] = eos
+            gen_dev = generator.device.type if generator is not None else device.type
+            self.seed_buf.copy_(torch.randint(0, 2 ** 62, (1,), device=gen_dev, generator=generator))
+            self.beam_first[0] = P
+            self._hip_beam(logits, p, 0, True)
+        else:
+            self.tok.copy_(beam_step_torch(logits, st, 0, p, generator).view(R, 1))
+            reorder_cache_torch(self.cache, torch.arange(R, device=device) // nb * nb)
+        # the captured launches hold these by value; the prompt length, EOS ids, seed and counters are device buffers set per call
+        gkey = (("hip", nb, K, int(eos.numel()), max_new_tokens, length_penalty, early_stopping, do_sample, temperature, top_k, p.top_p)
+                if hip else ("torch",))
+        if getattr(self, "_beam_gkey", None) != gkey:
+            self._beam_gkey = gkey
+            self._beam_graph = None
+        for t in range(1, max_new_tokens):
+            if t % self.sync_every == 0:
+                if bool(st.stopped(early_stopping)):
+                    break
+                mark("generate: rendezvous")
+            if not hip:
+                self.pos.fill_(P + t - 1)
+                if t > 1:
+                    self.posid.add_(1)
+            if self.use_graph:
+                if self._beam_graph is None:
+                    s = torch.cuda.Stream()
+                    s.wait_stream(torch.cuda.current_stream())
+                    with torch.cuda.stream(s):
+                        self._step()                              # warm-up of the forward only; state rewound below
+                        self._rewind(self.tok.shape[1])
+                    torch.cuda.current_stream().wait_stream(s)
+                    self._beam_graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(self._beam_graph, capture_error_mode="thread_local"):
+                        self._beam_logits = self._step()
+                        if hip:
+                            self._hip_beam(self._beam_logits, p, 1, False)
+                self._beam_graph.replay()
+                logits = self._beam_logits
+            else:
+                logits = self._step()
+                if hip:
+                    self._hip_beam(logits, p, 1, False)
+            if not hip:
+                self.tok.copy_(beam_step_torch(logits, st, t, p, generator).view(R, 1))
+                reorder_cache_torch(self.cache, st.par)
+        self.last_logits = logits
+        new_tokens = finalize(st, fill)
+        self._last["n_new"] = new_tokens.shape[1]
+        mark("generate: decode loop done")
+        return torch.cat([input_ids, new_tokens], dim=1) if input_ids is not None else new_tokens

@@ -299,7 +299,7 @@ class GraphLLMForCausalMLM(nn.Module):
         info = getattr(dec, "_last", None) if dec is not None else None
         tail = self.num_body_tokens + 1
         L = analysis.shape[1]
-        if (info is None or not info["from_ids"] or info.get("n_new") != info["max_new"] or L != info["max_new"] or L <= tail
+        if (info is None or info.get("beams", 1) > 1 or not info["from_ids"] or info.get("n_new") != info["max_new"] or L != info["max_new"] or L <= tail
                 or design_ids.shape[1] != input_ids.shape[1] + L):
             return None
         start_id = self.token_id_dict["<design_start>"]
