@@ -382,6 +382,35 @@ int ll_beam_step_bf16(const void *logits, int64_t ld, int B, int nb, int V, int 
 int ll_beam_kv_reorder_bf16(const int64_t *kv_ptrs, int n_tensors, int B, int nb, int nkv, int maxlen, int D, const int *par,
                             const int64_t *first, int from_first_beam, const int64_t *pos, void *stream);
 
+/* ---- weight-only MX quantisation of the decode step (quantization_bit: 8 | 4; llamole_amd/csrc/llm_wq.hip) -----------------------
+ * The Linear weights of a decoder layer are rounded once onto an OCP microscaling grid -- blocks of 32 consecutive elements along K, one
+ * E8M0 scale 2^e per block (byte e + 127), FP8 E4M3 (e4m3fn, max 448) elements at 8 bits, FP4 E2M1 (0, 0.5, 1, 1.5, 2, 3, 4, 6) at 4 --
+ * and decode calls of 1..16 token rows stream the packed codes (1.03125 / 0.53125 bytes per weight) instead of the bf16 matrix.
+ * Quantiser (exact, reproducible; llamole_amd/llm_quant.py:mx_round is its torch restatement): amax = max |w| of the block; e = the
+ * smallest integer with amax * 2^-e <= elem_max, taken from the exponent and mantissa bits of amax and clamped to [-117, 119] (8 bits) /
+ * [-125, 125] (4 bits) so that every dequantised value is a normal bf16 number, e = 0 for an all-zero block; element = w * 2^-e rounded to
+ * the nearest grid value, ties to even.  No element saturates.  code * 2^e is exactly a bf16 number: the dequantised matrix is an ordinary
+ * bf16 weight, and every bf16 kernel run on it computes the same model as the packed-code kernels.
+ * Layout of `packed` ([N, K] matrix, K % 32 == 0, ll_wq_bytes bytes, 16-byte aligned): N rows of K * bits / 8 code bytes (at 4 bits element
+ * 2i in the low nibble of byte i), then N rows of K / 32 scale bytes.  It belongs to the kernels; read it through ll_wq_dequantize_bf16.
+ *   ll_wq_bytes            size of the packed form (-1: bits not 4 | 8 or K not a multiple of 32).
+ *   ll_wq_quantize_bf16    W [N, K] bf16 (row stride ldw) -> packed; Wdq != NULL also receives the dequantised bf16 matrix (row stride
+ *                          lddq; may alias W; packed may then be NULL).  One launch, no host synchronisation.
+ *   ll_wq_dequantize_bf16  packed -> W [N, K] bf16, through the hardware conversions the kernels use.
+ *   ll_gemv_fused_wq       ll_gemv_fused_bf16 on a packed weight (M in 1..4; RMSNorm prologue with K <= 8192; plain /
+ *                          residual / SiLU*mul epilogues with the same bf16 roundings; LL_GEMV_SILU_MUL: packed holds 2N rows, gate rows
+ *                          then up rows); the M rows of x, each padded to a multiple of 1024 (8 bits) / 2048 (4 bits) elements, plus
+ *                          16 M bytes must fit the 160 KB of LDS.
+ *   ll_linear_rows16_wq    ll_linear_rows16_bf16 on a packed weight (M in 1..16): each wave expands the codes of its 16 weight rows to
+ *                          bf16 on the way into its LDS image; same prologue and epilogues. */
+int64_t ll_wq_bytes(int N, int K, int bits);
+int ll_wq_quantize_bf16(const void *W, int ldw, int N, int K, int bits, void *packed, void *Wdq, int lddq, void *stream);
+int ll_wq_dequantize_bf16(const void *packed, int N, int K, int bits, void *W, int ldw, void *stream);
+int ll_gemv_fused_wq(const void *x, int ldx, const void *packed, int bits, const float *bias, const void *norm_w, float eps,
+                     const void *residual, int ldr, void *out, int ldc, int M, int N, int K, int epi, void *stream);
+int ll_linear_rows16_wq(const void *x, int ldx, const void *packed, int bits, const float *bias, const void *norm_w, float eps,
+                        const void *residual, int ldr, void *out, int ldc, int M, int N, int K, int epi, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

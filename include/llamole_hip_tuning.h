@@ -108,6 +108,12 @@ int ll_set_rows64_ksplit(int ksg);
 int ll_rows64_bench(int M, int N, int K, int epi, int norm, int iters, int nweights, float *ms);
 /* Tuning: one-row GEMVs without RMSNorm and K >= 8192 (down_proj) stage x in LDS once per workgroup (default on; bit-identical). */
 int ll_set_gemv_stage(int on);
+/* ll_wq_bench : timing utility of the packed-weight kernels (HIP events, `nweights` distinct packed matrices so that the Infinity Cache
+ * does not serve them): kind 0 = ll_gemv_fused_wq (M 1..4), 1 = ll_linear_rows16_wq (M 1..16).  ll_set_wq_geometry : code bytes of a row per
+ * block (128; 256 at 8 bits only), waves per workgroup (4 | 8), consecutive waves that split K of one tile; (0, 0, 0) = chosen by shape;
+ * returns the previous setting. */
+int ll_wq_bench(int kind, int bits, int M, int N, int K, int epi, int norm, int iters, int nweights, float *ms);
+int ll_set_wq_geometry(int cseg, int waves, int ksplit);
 
 #ifdef __cplusplus
 }

@@ -103,6 +103,11 @@ SIGNATURES = {
     "ll_beam_state_bytes": (_I64, [_I, _I, _I, _I]),
     "ll_beam_step_bf16": (_I, [_P, _I64, _I, _I, _I, _I, _I, _P, _I64, _P, _I, _I, _F, _I, _I, _F, _I, _F, _P, _P, _P, _P, _I, _P]),
     "ll_beam_kv_reorder_bf16": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
+    "ll_wq_bytes": (_I64, [_I, _I, _I]),
+    "ll_wq_quantize_bf16": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "ll_wq_dequantize_bf16": (_I, [_P, _I, _I, _I, _P, _I, _P]),
+    "ll_gemv_fused_wq": (_I, [_P, _I, _P, _I, _P, _P, _F, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
+    "ll_linear_rows16_wq": (_I, [_P, _I, _P, _I, _P, _P, _F, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
 }
 
 # include/llamole_hip_tuning.h: exported by libllamole_hip_tuning.so only (the LL_TUNING=1 build of the same sources)
@@ -133,6 +138,8 @@ TUNING_SIGNATURES = {
     "ll_rows16_bench": (_I, [_I, _I, _I, _I, _I, _I, _I, C.POINTER(_F)]),
     "ll_set_rows64_ksplit": (_I, [_I]),
     "ll_rows64_bench": (_I, [_I, _I, _I, _I, _I, _I, _I, C.POINTER(_F)]),
+    "ll_wq_bench": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_F)]),
+    "ll_set_wq_geometry": (_I, [_I, _I, _I]),
 }
 
 _lib = None

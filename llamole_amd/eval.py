@@ -49,7 +49,9 @@ def load_yaml_args(path: str, overrides: Optional[Dict[str, Any]] = None):
         graph_predictor_path=cfg.get("graph_predictor_path"), graph_lm_connector_path=cfg.get("graph_lm_connector_path"),
         compute_dtype=torch.bfloat16 if bf16 else (torch.float16 if fp16 else torch.float32),
         disable_graph_model_gradient=cfg.get("disable_graph_model_gradient", True),
-        flash_attn=cfg.get("flash_attn", "auto"))
+        flash_attn=cfg.get("flash_attn", "auto"),
+        # reference hparams/model_args.py:112: 4 | 8 (there: bitsandbytes; here: the MX weight formats of llm_quant.py)
+        quantization_bit=cfg.get("quantization_bit"))
     data_args = SimpleNamespace(dataset=cfg.get("dataset"), dataset_dir=cfg.get("dataset_dir", "data"),
                                 template=cfg.get("template"), cutoff_len=int(cfg.get("cutoff_len", 1024)),
                                 learned_query_size=int(cfg.get("learned_query_size", 8)),
@@ -202,6 +204,8 @@ def run_eval(config_path: str, overrides: Optional[Dict[str, Any]] = None) -> Di
     """Entry used by ``python main.py eval cfg.yaml``."""
     from .modeling_llamole import GraphLLMForCausalMLM
     model_args, data_args, training_args, finetuning_args, generating_args = load_yaml_args(config_path, overrides)
+    from .llm_quant import check_quantization_bit
+    quantization_bit = check_quantization_bit(model_args.quantization_bit)      # refused before anything is loaded
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     from .distributed import force_dist
     if world > 1 or force_dist():
@@ -229,7 +233,7 @@ def run_eval(config_path: str, overrides: Optional[Dict[str, Any]] = None) -> Di
     model = GraphLLMForCausalMLM.from_pretrained(tokenizer, model_args, data_args, training_args, finetuning_args,
                                                  load_adapter=bool(model_args.adapter_name_or_path))
     model.eval()
-    accel = model.enable_mi355x_decode()
+    accel = model.enable_mi355x_decode(quantization_bit=quantization_bit)      # from_pretrained merged the adapter: the merged weights are rounded
     model.batch_retro = bool(getattr(generating_args, "batch_retro", False) or (overrides or {}).get("batch_retro", False))
     if rank == 0:
         print(json.dumps({"llm_acceleration": accel}))

@@ -20,6 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from .llm_quant import check_quantization_bit, quantize_llm, reround_changed
 
 MAX_ROWS = 128           # GEMV / skinny-GEMM path under nn.Linear (128-token prefill: 8.7 ms vs 10.0 ms on hipBLASLt, tools/prefill_probe.py)
 MAX_ROWS16 = 16         # ll_linear_rows16_bf16: one MFMA column block of token rows (batched decode: 3..16 sequences)
@@ -38,6 +39,24 @@ MAX_EW_ROWS = 1 << 20
 # picks a 256 x 16 tile there and takes 32 ms (8.6 TFLOP/s); the LDS-DMA ring GEMM streams the 1.09 GB of weights once
 MAX_WIDE_ROWS, WIDE_N = 1024, 65536
 PREFILL_SPLITK = os.environ.get("LLAMOLE_PREFILL_SPLITK", "1") != "0"
+# quantization_bit (llm_quant.py): at which token-row counts a matrix of a fused layer ("qkv", "o", "gate_up", "down") streams its packed MX
+# codes -- up to FMA_GEMV_ROWS rows through ll_gemv_fused_wq, above through ll_linear_rows16_wq.  A row count is listed only where the
+# packed kernel beat the bf16 kernel it replaces by more than the spread of the alternated repeats (tools/wq_sweep.py,
+# profiles/decode_quant_kernels.txt; decode token: profiles/decode_quant_time.txt); everywhere else the bf16 kernels run on the
+# dequantised weights, which is the same model.  The table was measured with FMA_GEMV_ROWS = 2: another value switches the packed route off.
+WQ_MATRICES = ("qkv", "o", "gate_up", "down")
+# Row counts that won on BOTH Qwen2-7B and Llama-3.1-8B shapes; o_proj, whose verdict flips between neighbouring row counts (within 4 %
+# of the bf16 kernel either way), stays on the bf16 kernel.
+WQ_ROUTES = {
+    (8, "qkv"): frozenset({2}), (8, "o"): frozenset(), (8, "gate_up"): frozenset(range(2, 17)), (8, "down"): frozenset(range(2, 17)),
+    (4, "qkv"): frozenset({2}), (4, "o"): frozenset(), (4, "gate_up"): frozenset({1, 2}), (4, "down"): frozenset(range(1, 17)),
+}
+
+
+def all_packed_routes() -> dict:
+    """Every (bits, matrix) at every row count 1..16: what the tests and the A/B timing put into ``WQ_ROUTES`` to run the packed kernels
+    whatever the measured routing switched on."""
+    return {(b, m): frozenset(range(1, MAX_ROWS16 + 1)) for b in (8, 4) for m in WQ_MATRICES}
 
 
 def _versions(*tensors):
@@ -64,6 +83,32 @@ class _Packed64:
         rc = lib.ll_rows64_pack_bf16(w.data_ptr(), w.stride(0), self.rows, self.K, self.t.data_ptr(), torch.cuda.current_stream().cuda_stream)
         if rc != 0:
             _lib.check(rc, "ll_rows64_pack_bf16")
+        self.key = key
+        return True
+
+
+class _PackedWQ:
+    """The MX codes + scale bytes of a (rounded) bf16 weight for ll_gemv_fused_wq / ll_linear_rows16_wq, made by ll_wq_quantize_bf16.  Like
+    ``_Packed64`` the copy follows its source: ``sync`` re-quantises IN PLACE when the key changed (captured graphs hold its address)."""
+
+    def __init__(self, lib, w: torch.Tensor, bits: int, key):
+        self.rows, self.K = w.shape
+        self.bits = bits
+        n = int(lib.ll_wq_bytes(self.rows, self.K, bits))
+        if n < 0:
+            raise ValueError(f"ll_wq_quantize_bf16: K={self.K} must be a multiple of 32 and bits={bits} one of 4, 8")
+        self.t = torch.empty(n, dtype=torch.uint8, device=w.device)
+        self.key = None
+        self.sync(lib, w, key)
+
+    def sync(self, lib, w: torch.Tensor, key) -> bool:
+        if self.key == key:
+            return False
+        assert w.shape == (self.rows, self.K) and w.stride(1) == 1
+        rc = lib.ll_wq_quantize_bf16(w.data_ptr(), w.stride(0), self.rows, self.K, self.bits, self.t.data_ptr(), None, 0,
+                                     torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            _lib.check(rc, "ll_wq_quantize_bf16")
         self.key = key
         return True
 
@@ -183,6 +228,9 @@ def refresh_weight_copies(model: nn.Module) -> int:
     MLP gate/up + attention q/k/v weights in memory (~8.5 GB for Qwen2-7B in bf16)."""
     n = 0
     with torch.no_grad():
+        # quantization_bit: a rounded source weight that changed is rounded again first (in place; its key is recorded after the write), so
+        # that every copy below is made from rounded weights
+        n += reround_changed(model)
         for mod in model.modules():
             d = mod.__dict__
             q = getattr(mod, "q_proj", None)
@@ -224,6 +272,8 @@ def refresh_weight_copies(model: nn.Module) -> int:
             st = mod.__dict__.get("_ll_fused")
             if st is not None and st.p64 is not None:
                 n += int(st.packed64(sync=True))
+            if st is not None and st.pq is not None:
+                n += int(st.sync_wq())
     return n
 
 
@@ -590,6 +640,17 @@ class _FusedLayer:
         self.stream_ok = self.H % 32 == 0 and self.nq % 32 == 0 and self.I % 32 == 0 and self.n1.weight.dtype == torch.bfloat16
         self._mods = (q, k, v, o, mlp.gate_proj, mlp.up_proj, mlp.down_proj)
         self.p64 = None         # packed copies of the four matrices for 17..64 rows (made at the first such step)
+        # quantization_bit: the MX codes of [q|k|v], o_proj, [gate|up], down_proj (made from the rounded bf16 matrices, which stay: they serve the
+        # prefill and 17..64 rows); None = the layer runs on bf16 weights (not quantised, or a K that is not a multiple of 32)
+        bits = {m.__dict__.get("_ll_wq_bits") for m in self._mods}
+        self.wq_bits = bits.pop() if len(bits) == 1 else None
+        self.pq = None
+        self.use_wq = True      # off: the bf16 kernels on the dequantised weights (tests, A/B timing)
+        if self.wq_bits is not None and self.stream_ok and self.I % 32 == 0:
+            self.pq = tuple(_PackedWQ(lib, w, self.wq_bits, key) for w, key in zip((self.wqkv, self.wo, self.wgu, self.wdown), self._keys64()))
+
+    def sync_wq(self) -> int:
+        return sum(p.sync(self.lib, w, key) for p, w, key in zip(self.pq, (self.wqkv, self.wo, self.wgu, self.wdown), self._keys64()))
 
     def _keys64(self):
         q, k, v, o, g, u, d = self._mods
@@ -624,8 +685,23 @@ class _FusedLayer:
                 and cos.dim() == 3 and cos.shape[1] == 1 and cos.shape[2] == self.D and cos.stride(2) == 1
                 and pe[1].stride() == cos.stride() and h.is_contiguous())
 
-    def _gemv(self, x, w, bias, norm_w, eps, res, N, K, epi):
+    def _gemv_wq(self, x, pk, bias, norm_w, eps, res, N, K, epi):
+        """1..16 token rows on the packed MX codes ``pk``: the f32-FMA GEMV up to FMA_GEMV_ROWS rows, the MFMA weight stream beyond."""
         M = x.shape[0]
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+        name = "ll_linear_rows16_wq" if M > FMA_GEMV_ROWS else "ll_gemv_fused_wq"
+        rc = getattr(self.lib, name)(x.data_ptr(), x.stride(0), pk.t.data_ptr(), pk.bits, bias.data_ptr() if bias is not None else None,
+                                     norm_w.data_ptr() if norm_w is not None else None, eps,
+                                     res.data_ptr() if res is not None else None, res.stride(0) if res is not None else 0,
+                                     out.data_ptr(), N, M, N, K, epi, torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            _lib.check(rc, name)
+        return out
+
+    def _gemv(self, x, w, bias, norm_w, eps, res, N, K, epi, pk=None, which=None):
+        M = x.shape[0]
+        if pk is not None and self.use_wq and FMA_GEMV_ROWS == 2 and M in WQ_ROUTES.get((pk.bits, which), ()):
+            return self._gemv_wq(x, pk, bias, norm_w, eps, res, N, K, epi)
         out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
         if M > FMA_GEMV_ROWS and self.stream_ok:
             rc = self.lib.ll_linear_rows16_bf16(x.data_ptr(), x.stride(0), w.data_ptr(), K, bias.data_ptr() if bias is not None else None,
@@ -686,7 +762,8 @@ class _FusedLayer:
         pos = cache.layers[0].cumulative_length
         cos, sin = pe
         nqkv = self.nq + 2 * self.nkv_dim
-        qkv = self._gemv(x, self.wqkv, self.bqkv, self.n1.weight, self.eps1, None, nqkv, H, 0)
+        pq = self.pq or (None, None, None, None)
+        qkv = self._gemv(x, self.wqkv, self.bqkv, self.n1.weight, self.eps1, None, nqkv, H, 0, pq[0], "qkv")
         att = torch.empty(B, self.nq, dtype=torch.bfloat16, device=h.device)
         rc = self.lib.ll_decode_attn_rope_bf16(qkv.data_ptr(), nqkv, cos.data_ptr(), sin.data_ptr(),
                                                0 if cos.shape[0] == 1 else cos.stride(0), cl.keys.data_ptr(), cl.values.data_ptr(),
@@ -694,9 +771,9 @@ class _FusedLayer:
                                                cl.keys.shape[2], self.D, self.scaling, torch.cuda.current_stream().cuda_stream)
         if rc != 0:
             _lib.check(rc, "ll_decode_attn_rope_bf16")
-        h1 = self._gemv(att, self.wo, self.bo, None, 0.0, x, H, self.nq, 1)
-        act = self._gemv(h1, self.wgu, None, self.n2.weight, self.eps2, None, self.I, H, 2)
-        h2 = self._gemv(act, self.wdown, None, None, 0.0, h1, H, self.I, 1)
+        h1 = self._gemv(att, self.wo, self.bo, None, 0.0, x, H, self.nq, 1, pq[1], "o")
+        act = self._gemv(h1, self.wgu, None, self.n2.weight, self.eps2, None, self.I, H, 2, pq[2], "gate_up")
+        h2 = self._gemv(act, self.wdown, None, None, 0.0, h1, H, self.I, 1, pq[3], "down")
         return h2.view(B, 1, H)
 
 
@@ -709,16 +786,17 @@ class _FusedLayer:
         pos = cache.layers[0].cumulative_length
         cos, sin = pe
         nqkv = self.nq + 2 * self.nkv_dim
-        qkv = self._gemv(x, self.wqkv, self.bqkv, self.n1.weight, self.eps1, None, nqkv, H, 0)
+        pq = self.pq or (None, None, None, None)
+        qkv = self._gemv(x, self.wqkv, self.bqkv, self.n1.weight, self.eps1, None, nqkv, H, 0, pq[0], "qkv")
         att = torch.empty(R, self.nq, dtype=torch.bfloat16, device=h.device)
         rc = self.lib.ll_suffix_attn_rope_bf16(qkv.data_ptr(), nqkv, cos.data_ptr(), sin.data_ptr(), cl.keys.data_ptr(), cl.values.data_ptr(),
                                                pos.data_ptr(), mask.data_ptr(), att.data_ptr(), B, S, self.nh, self.nkv, cl.keys.shape[2],
                                                self.D, self.scaling, torch.cuda.current_stream().cuda_stream)
         if rc != 0:
             _lib.check(rc, "ll_suffix_attn_rope_bf16")
-        h1 = self._gemv(att, self.wo, self.bo, None, 0.0, x, H, self.nq, 1)
-        act = self._gemv(h1, self.wgu, None, self.n2.weight, self.eps2, None, self.I, H, 2)
-        h2 = self._gemv(act, self.wdown, None, None, 0.0, h1, H, self.I, 1)
+        h1 = self._gemv(att, self.wo, self.bo, None, 0.0, x, H, self.nq, 1, pq[1], "o")
+        act = self._gemv(h1, self.wgu, None, self.n2.weight, self.eps2, None, self.I, H, 2, pq[2], "gate_up")
+        h2 = self._gemv(act, self.wdown, None, None, 0.0, h1, H, self.I, 1, pq[3], "down")
         return h2.view(B, S, H)
 
 
@@ -906,12 +984,34 @@ def restore_model_decode(model: nn.Module) -> None:
 
 
 # ------------------------------------------------------------------------------------------ one call for the whole stack
-def accelerate_llm(model: nn.Module, linears: bool = True, fuse: bool = True, layers: bool = True, model_decode: bool = True) -> dict:
+def set_packed_route(model: nn.Module, on: bool) -> int:
+    """Switch the packed-code route of every quantised fused layer: off = the bf16 five-launch layers on the dequantised weights (the same
+    model).  Returns the number of layers that hold packed codes."""
+    n = 0
+    base = getattr(model, "model", model)
+    for layer in getattr(base, "layers", None) or []:
+        st = layer.__dict__.get("_ll_fused")
+        if st is not None and st.pq is not None:
+            st.use_wq = bool(on)
+            n += 1
+    return n
+
+
+def accelerate_llm(model: nn.Module, linears: bool = True, fuse: bool = True, layers: bool = True, model_decode: bool = True,
+                   quantization_bit=None) -> dict:
     """Apply the decode acceleration stack to an (untouched) HF Llama-family causal LM on a HIP device and report what took
     effect: GEMV under nn.Linear -> fused RMSNorm / rotary / SiLU*mul and q|k|v, gate|up fusion -> decode attention through
     the AttentionInterface registry -> five-launch decoder layers -> one-launch decode prologue.  Every stage falls back to
-    the HF code for shapes or architectures it does not cover; pair it with ``GraphedDecoder(..., fused_cache=True)``."""
+    the HF code for shapes or architectures it does not cover; pair it with ``GraphedDecoder(..., fused_cache=True)``.
+    ``quantization_bit`` 8 | 4 (None: the environment variable LLAMOLE_QUANT_BITS, unset by default) first rounds the decoder-layer Linears
+    onto the MX grid in place (``llm_quant.quantize_llm``; on a CPU model that is all it does), so the concatenated copies are made from
+    rounded weights; the fused layers then keep the packed codes and stream them at 1..16 token rows."""
     info: dict = {"linears": 0}
+    if quantization_bit is None and os.environ.get("LLAMOLE_QUANT_BITS"):
+        quantization_bit = int(os.environ["LLAMOLE_QUANT_BITS"])
+    bits = check_quantization_bit(quantization_bit)
+    if bits is not None:
+        info["quantization"] = quantize_llm(model, bits)
     if not next(model.parameters()).is_cuda:
         return info
     if linears:
@@ -923,4 +1023,13 @@ def accelerate_llm(model: nn.Module, linears: bool = True, fuse: bool = True, la
             info["decoder_layers_5_launches"] = fuse_decoder_layers(model)
             if model_decode:
                 info["decode_prologue_1_launch"] = fuse_model_decode(model)
+    if bits is not None:
+        base = getattr(model, "model", model)
+        fused = [l.__dict__.get("_ll_fused") for l in (getattr(base, "layers", None) or [])]
+        q = info["quantization"]
+        q["packed_layers"] = sum(1 for st in fused if st is not None and st.pq is not None)
+        # layers without packed codes (not fused, or a size that is not a multiple of 32) run the bf16 kernels on their dequantised weights
+        q["bf16_layers"] = len(fused) - q["packed_layers"]
+        # token-row counts at which each matrix streams its packed codes; every other call runs the bf16 kernels on the dequantised weights
+        q["packed_routes"] = {m: (sorted(WQ_ROUTES.get((bits, m), ())) if FMA_GEMV_ROWS == 2 else []) for m in WQ_MATRICES}
     return info

@@ -79,12 +79,13 @@ class GraphLLMForCausalMLM(nn.Module):
         self.reuse_query_kv = reuse_query_kv
         return self
 
-    def enable_mi355x_decode(self, use_graph: bool = True, **kw) -> dict:
+    def enable_mi355x_decode(self, use_graph: bool = True, quantization_bit: Optional[int] = None, **kw) -> dict:
         """The whole LLM-side stack in one call (what bench.py measures): HIP kernels under the HF modules
         (llm_accel.accelerate_llm) + hipGraph decode with the fused KV append and in-graph sampler.  Returns the report of
-        what took effect; on a CPU model it only installs the (eager) static-cache decoder."""
+        what took effect; on a CPU model it only installs the (eager) static-cache decoder.  ``quantization_bit`` 8 | 4 rounds the
+        decoder-layer Linears onto the MX grid first (llm_quant.py; also on a CPU model) and decodes from the packed codes."""
         from .llm_accel import accelerate_llm
-        info = accelerate_llm(self.language_model)
+        info = accelerate_llm(self.language_model, quantization_bit=quantization_bit)
         self.enable_graphed_decode(use_graph=use_graph, fused_cache=bool(info.get("decode_attention")), **kw)
         return info
 

@@ -160,6 +160,9 @@ def run_train(config_path: str, overrides: Optional[Dict[str, Any]] = None) -> D
         setattr(finetuning_args, k, float(cfg.get(k, 1)))
     if cfg.get("finetuning_type", "lora") != "lora":
         raise ValueError("only finetuning_type: lora is provided (the reference's shipped training configs)")
+    if model_args.quantization_bit is not None:
+        raise ValueError("quantization_bit is an evaluation option here (weight-only MX rounding of the decode path); training on a quantised "
+                         "base model (QLoRA) is not provided")
     out_dir = cfg.get("output_dir")
     if not out_dir:
         raise ValueError("output_dir is required")
