@@ -275,6 +275,20 @@ int ll_suffix_prologue(const int64_t *position_ids, const float *inv_freq, float
                        void *stream);
 int ll_suffix_attn_rope_bf16(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, void *Kc, void *Vc, const int64_t *pos,
                              const void *mask, void *out, int B, int S, int nh, int nkv, int maxlen, int D, float scale, void *stream);
+/* ll_decode_prologue_dyn / ll_suffix_prologue_dyn : the two prologues for dynamic NTK rope (transformers dynamic_rope_update) without its
+ *     host read of the position ids.  With L = max(position_ids of the call) + 1, read on the device by every workgroup, the frequencies are
+ *     inv_freq0 [D/2] (the module's constructed original_inv_freq) while L <= max_pos (= config.max_position_embeddings) and row
+ *     L - max_pos - 1 of table [table_rows, D/2] f32 beyond: row j = ROPE_INIT_FUNCTIONS["dynamic"](config, seq_len = max_pos + 1 + j).
+ *     Everything else is ll_decode_prologue / ll_suffix_prologue, bit for bit.  table_rows >= maxlen - max_pos is required (LL_EINVAL
+ *     otherwise: the table must cover every length the cache can reach); table may be NULL when maxlen <= max_pos.  The scaled types whose
+ *     frequencies are fixed at construction (linear, llama3, yarn) need no entry point of their own: they are ll_decode_prologue with
+ *     the module's inv_freq and attention_scaling. */
+int ll_decode_prologue_dyn(const int64_t *position_ids, const float *inv_freq0, const float *table, int max_pos, int table_rows,
+                           float attention_scaling, const int64_t *mask2d, int64_t mask_stride, const int64_t *pos, void *cos, void *sin,
+                           void *mask_out, int B, int D, int maxlen, void *stream);
+int ll_suffix_prologue_dyn(const int64_t *position_ids, const float *inv_freq0, const float *table, int max_pos, int table_rows,
+                           float attention_scaling, const int64_t *mask2d, int64_t mask_stride, const int64_t *pos, void *cos, void *sin,
+                           void *mask_out, int B, int S, int D, int maxlen, void *stream);
 
 /* ll_linear_rows16_bf16 : out[M,N] = epilogue(x[M,K] . W^T + bias), M in 1..16, K % 32 == 0, bf16 operands, f32 accumulation on MFMA:
  *     the nn.Linear of a batched decode step (5..16 sequences: lock-step A* searches, several prompts per GPU) as a weight

@@ -614,12 +614,12 @@ __global__ __launch_bounds__(64 * W) void decode_attn_rope_gqa_kernel(const bf16
 
 // Per-token prologue of the decode step: what Qwen2RotaryEmbedding.forward (freqs = inv_freq * position, cos/sin in f32,
 // * attention_scaling, cast to bf16) and create_causal_mask (key j visible iff j <= query position and not padding) compute
-// with ~12 small ATen launches, as one.  grid B.
-__global__ __launch_bounds__(256) void decode_prologue_kernel(const long long *__restrict__ posid, const float *__restrict__ inv_freq,
-                                                              float scaling, const long long *__restrict__ mask2d, int64_t ms,
-                                                              const long long *__restrict__ pos_ptr, bf16_t *__restrict__ cos_o,
-                                                              bf16_t *__restrict__ sin_o, unsigned char *__restrict__ mask_o,
-                                                              int D, int maxlen, int S) {
+// with ~12 small ATen launches, as one.  grid B.  The scaled rope types whose inv_freq / attention_scaling are fixed at construction
+// (linear, llama3, yarn) are this kernel with other constants.
+__device__ __forceinline__ void prologue_row(const long long *__restrict__ posid, const float *__restrict__ inv_freq, float scaling,
+                                             const long long *__restrict__ mask2d, int64_t ms, const long long *__restrict__ pos_ptr,
+                                             bf16_t *__restrict__ cos_o, bf16_t *__restrict__ sin_o, unsigned char *__restrict__ mask_o,
+                                             int D, int maxlen, int S) {
     // row r = b*S + s: the s-th new position of sequence b (S = 1: a decode step)
     const int r = blockIdx.x, tid = threadIdx.x;
     const int b = r / S, s = r - b * S;
@@ -634,6 +634,44 @@ __global__ __launch_bounds__(256) void decode_prologue_kernel(const long long *_
     }
     const long long p = *pos_ptr + s;
     for (int j = tid; j < maxlen; j += 256) mask_o[(int64_t)r * maxlen + j] = (j <= p && mask2d[b * ms + j] != 0) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void decode_prologue_kernel(const long long *__restrict__ posid, const float *__restrict__ inv_freq,
+                                                              float scaling, const long long *__restrict__ mask2d, int64_t ms,
+                                                              const long long *__restrict__ pos_ptr, bf16_t *__restrict__ cos_o,
+                                                              bf16_t *__restrict__ sin_o, unsigned char *__restrict__ mask_o,
+                                                              int D, int maxlen, int S) {
+    prologue_row(posid, inv_freq, scaling, mask2d, ms, pos_ptr, cos_o, sin_o, mask_o, D, maxlen, S);
+}
+
+// Dynamic NTK rope (transformers dynamic_rope_update) without its host read: with L = max(position ids of the call) + 1 the frequencies are
+// inv_freq0 (the constructed ones) while L <= max_pos and row L - max_pos - 1 of ``table`` ([table_rows, D/2] f32: HF's own init function at
+// sequence lengths max_pos + 1 ...) beyond.  Every workgroup reduces the call's n = gridDim.x position ids itself (n <= 64 at decode, <= 16
+// for the suffix: no cross-workgroup traffic), then runs the row exactly as decode_prologue_kernel does.
+__global__ __launch_bounds__(256) void decode_prologue_dyn_kernel(const long long *__restrict__ posid, const float *__restrict__ inv_freq0,
+                                                                  const float *__restrict__ table, int max_pos, int table_rows,
+                                                                  float scaling, const long long *__restrict__ mask2d, int64_t ms,
+                                                                  const long long *__restrict__ pos_ptr, bf16_t *__restrict__ cos_o,
+                                                                  bf16_t *__restrict__ sin_o, unsigned char *__restrict__ mask_o,
+                                                                  int D, int maxlen, int S) {
+    __shared__ long long red[256];
+    const int tid = threadIdx.x, n = gridDim.x;
+    long long m = posid[0];
+    for (int i = tid; i < n; i += 256) m = posid[i] > m ? posid[i] : m;
+    red[tid] = m;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o && red[tid + o] > red[tid]) red[tid] = red[tid + o];
+        __syncthreads();
+    }
+    const long long L = red[0] + 1;
+    const float *inv_freq = inv_freq0;
+    if (L > max_pos && table_rows > 0) {
+        long long row = L - max_pos - 1;
+        if (row > table_rows - 1) row = table_rows - 1;      // a position id past the cache length: stay inside the table
+        inv_freq = table + row * (D / 2);
+    }
+    prologue_row(posid, inv_freq, scaling, mask2d, ms, pos_ptr, cos_o, sin_o, mask_o, D, maxlen, S);
 }
 
 static int g_gemv_nt = 1;   // non-temporal weight loads (tools/gemv_fused_sweep.py)
@@ -787,6 +825,35 @@ int ll_suffix_prologue(const int64_t *position_ids, const float *inv_freq, float
                        (unsigned char *)mask_out, D, maxlen, S);
     LL_LAUNCH_CHECK();
     return LL_OK;
+}
+
+static int prologue_dyn(const char *who, const int64_t *position_ids, const float *inv_freq0, const float *table, int max_pos, int table_rows,
+                        float attention_scaling, const int64_t *mask2d, int64_t mask_stride, const int64_t *pos, void *cos, void *sin,
+                        void *mask_out, int B, int S, int D, int maxlen, void *stream) {
+    LL_CHECK(position_ids && inv_freq0 && mask2d && pos && cos && sin && mask_out, "%s: null argument", who);
+    LL_CHECK(B >= 1 && S >= 1 && D >= 2 && D % 2 == 0 && D <= 512 && maxlen >= 1 && max_pos >= 1 && table_rows >= 0, "%s: unsupported shape", who);
+    // every sequence length that a cache of maxlen slots can reach needs its row
+    LL_CHECK(maxlen <= max_pos || (table && table_rows >= maxlen - max_pos),
+             "%s: table_rows < maxlen - max_pos (the frequency table does not cover the cache length)", who);
+    hipLaunchKernelGGL(decode_prologue_dyn_kernel, dim3(B * S), dim3(256), 0, (hipStream_t)stream, (const long long *)position_ids, inv_freq0,
+                       table, max_pos, table ? table_rows : 0, attention_scaling, (const long long *)mask2d, mask_stride,
+                       (const long long *)pos, (bf16_t *)cos, (bf16_t *)sin, (unsigned char *)mask_out, D, maxlen, S);
+    LL_LAUNCH_CHECK();
+    return LL_OK;
+}
+
+int ll_decode_prologue_dyn(const int64_t *position_ids, const float *inv_freq0, const float *table, int max_pos, int table_rows,
+                           float attention_scaling, const int64_t *mask2d, int64_t mask_stride, const int64_t *pos, void *cos, void *sin,
+                           void *mask_out, int B, int D, int maxlen, void *stream) {
+    return prologue_dyn("ll_decode_prologue_dyn", position_ids, inv_freq0, table, max_pos, table_rows, attention_scaling, mask2d, mask_stride,
+                        pos, cos, sin, mask_out, B, 1, D, maxlen, stream);
+}
+
+int ll_suffix_prologue_dyn(const int64_t *position_ids, const float *inv_freq0, const float *table, int max_pos, int table_rows,
+                           float attention_scaling, const int64_t *mask2d, int64_t mask_stride, const int64_t *pos, void *cos, void *sin,
+                           void *mask_out, int B, int S, int D, int maxlen, void *stream) {
+    return prologue_dyn("ll_suffix_prologue_dyn", position_ids, inv_freq0, table, max_pos, table_rows, attention_scaling, mask2d, mask_stride,
+                        pos, cos, sin, mask_out, B, S, D, maxlen, stream);
 }
 
 int ll_suffix_attn_rope_bf16(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, void *Kc, void *Vc, const int64_t *pos,

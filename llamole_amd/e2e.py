@@ -36,6 +36,11 @@ LLM_CONFIGS = {
                  rms_norm_eps=1e-6, tie_word_embeddings=False),
 }
 
+# rope_parameters of the published meta-llama/Meta-Llama-3.1-8B-Instruct config.json (rope_scaling there): the "llama-3.1-8b" entry above has the
+# published widths with default rope; build_llm("llama-3.1-8b", ..., rope_parameters=LLAMA31_ROPE) is the checkpoint's rotary module
+LLAMA31_ROPE = dict(rope_type="llama3", rope_theta=500000.0, factor=8.0, low_freq_factor=1.0, high_freq_factor=4.0,
+                    original_max_position_embeddings=8192)
+
 
 class SyntheticTokenizer:
     """Just enough tokenizer for synthetic-id workloads: eos id, special-token ids, trivial decode."""

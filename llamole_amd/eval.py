@@ -51,7 +51,9 @@ def load_yaml_args(path: str, overrides: Optional[Dict[str, Any]] = None):
         disable_graph_model_gradient=cfg.get("disable_graph_model_gradient", True),
         flash_attn=cfg.get("flash_attn", "auto"),
         # reference hparams/model_args.py:112: 4 | 8 (there: bitsandbytes; here: the MX weight formats of llm_quant.py)
-        quantization_bit=cfg.get("quantization_bit"))
+        quantization_bit=cfg.get("quantization_bit"),
+        # reference hparams/model_args.py:128: linear | dynamic, applied to the LLM config before the weights are loaded (rope.configure_rope)
+        rope_scaling=cfg.get("rope_scaling"))
     data_args = SimpleNamespace(dataset=cfg.get("dataset"), dataset_dir=cfg.get("dataset_dir", "data"),
                                 template=cfg.get("template"), cutoff_len=int(cfg.get("cutoff_len", 1024)),
                                 learned_query_size=int(cfg.get("learned_query_size", 8)),
@@ -206,6 +208,8 @@ def run_eval(config_path: str, overrides: Optional[Dict[str, Any]] = None) -> Di
     model_args, data_args, training_args, finetuning_args, generating_args = load_yaml_args(config_path, overrides)
     from .llm_quant import check_quantization_bit
     quantization_bit = check_quantization_bit(model_args.quantization_bit)      # refused before anything is loaded
+    from .rope import check_rope_scaling
+    check_rope_scaling(model_args.rope_scaling)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     from .distributed import force_dist
     if world > 1 or force_dist():

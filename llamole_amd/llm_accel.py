@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import os
 import types
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -21,6 +22,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from .llm_quant import check_quantization_bit, quantize_llm, reround_changed
+from .rope import STATIC_ROPE_TYPES, dynamic_inv_freq_table
 
 MAX_ROWS = 128           # GEMV / skinny-GEMM path under nn.Linear (128-token prefill: 8.7 ms vs 10.0 ms on hipBLASLt, tools/prefill_probe.py)
 MAX_ROWS16 = 16         # ll_linear_rows16_bf16: one MFMA column block of token rows (batched decode: 3..16 sequences)
@@ -860,6 +862,7 @@ def _model_forward(self, input_ids=None, attention_mask=None, position_ids=None,
     prologue launch (rotary cos/sin + causal/padding key mask, instead of ~12 ATen launches of rotary_emb and
     create_causal_mask), the five-launch layers, final norm.  Anything else goes to the original forward."""
     st = self._ll_decode
+    st["served"] = False          # whether this call ran on the fused path (GraphedDecoder reads it after its eager warm-up step)
     layers = self.layers[: self.config.num_hidden_layers]
     if (input_ids is not None and inputs_embeds is None and input_ids.dim() == 2 and input_ids.shape[1] == 1
             and input_ids.shape[0] <= MAX_STREAM_ROWS and input_ids.is_cuda and not torch.is_grad_enabled() and past_key_values is not None
@@ -876,14 +879,24 @@ def _model_forward(self, input_ids=None, attention_mask=None, position_ids=None,
             cos = torch.empty(B, 1, D, dtype=torch.bfloat16, device=dev)
             sin = torch.empty(B, 1, D, dtype=torch.bfloat16, device=dev)
             mask = torch.empty(B, 1, 1, maxlen, dtype=torch.bool, device=dev)
-            inv_freq = self.rotary_emb.inv_freq
             pos = past_key_values.layers[0].cumulative_length
             posid = position_ids.contiguous()
-            rc = st["lib"].ll_decode_prologue(posid.data_ptr(), inv_freq.data_ptr(), float(self.rotary_emb.attention_scaling),
-                                              attention_mask.data_ptr(), attention_mask.stride(0), pos.data_ptr(), cos.data_ptr(),
-                                              sin.data_ptr(), mask.data_ptr(), B, D, maxlen, torch.cuda.current_stream().cuda_stream)
-            if rc != 0:
-                _lib.check(rc, "ll_decode_prologue")
+            if st.get("dyn") is None:
+                inv_freq = self.rotary_emb.inv_freq
+                rc = st["lib"].ll_decode_prologue(posid.data_ptr(), inv_freq.data_ptr(), float(self.rotary_emb.attention_scaling),
+                                                  attention_mask.data_ptr(), attention_mask.stride(0), pos.data_ptr(), cos.data_ptr(),
+                                                  sin.data_ptr(), mask.data_ptr(), B, D, maxlen, torch.cuda.current_stream().cuda_stream)
+                if rc != 0:
+                    _lib.check(rc, "ll_decode_prologue")
+            else:
+                # dynamic NTK: the kernel picks the frequencies from the call's own position ids (never rotary_emb.inv_freq, which HF replaces)
+                inv0, table, rows = _dyn_freqs(self, st, maxlen)
+                rc = st["lib"].ll_decode_prologue_dyn(posid.data_ptr(), inv0.data_ptr(), table.data_ptr() if table is not None else None,
+                                                      st["dyn"]["max_pos"], rows, 1.0, attention_mask.data_ptr(), attention_mask.stride(0),
+                                                      pos.data_ptr(), cos.data_ptr(), sin.data_ptr(), mask.data_ptr(), B, D, maxlen,
+                                                      torch.cuda.current_stream().cuda_stream)
+                if rc != 0:
+                    _lib.check(rc, "ll_decode_prologue_dyn")
             pe = (cos, sin)
             if layers[0]._ll_fused.eligible(h, mask, past_key_values, pe):
                 if B > MAX_ROWS16:
@@ -896,11 +909,13 @@ def _model_forward(self, input_ids=None, attention_mask=None, position_ids=None,
                     for layer in layers:
                         h = layer._ll_fused.run(h, mask, past_key_values, pe)
                 h = self.norm(h)
+                st["served"] = True
                 from transformers.modeling_outputs import BaseModelOutputWithPast
                 return BaseModelOutputWithPast(last_hidden_state=h, past_key_values=past_key_values if use_cache else None)
     if st.get("suffix") and input_ids is not None and inputs_embeds is None and input_ids.dim() == 2:
         out = _suffix_forward(self, st, layers, input_ids, attention_mask, position_ids, past_key_values, use_cache, kwargs)
         if out is not None:
+            st["served"] = True
             return out
     return self._ll_model_orig(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
                                past_key_values=past_key_values, inputs_embeds=inputs_embeds, use_cache=use_cache, **kwargs)
@@ -931,11 +946,20 @@ def _suffix_forward(self, st, layers, input_ids, attention_mask, position_ids, c
     sin = torch.empty(R, D, dtype=torch.bfloat16, device=dev)
     mask = torch.empty(R, maxlen, dtype=torch.bool, device=dev)
     posid = position_ids.contiguous()
-    rc = st["lib"].ll_suffix_prologue(posid.data_ptr(), self.rotary_emb.inv_freq.data_ptr(), float(self.rotary_emb.attention_scaling),
-                                      attention_mask.data_ptr(), attention_mask.stride(0), clayers[0].cumulative_length.data_ptr(),
-                                      cos.data_ptr(), sin.data_ptr(), mask.data_ptr(), B, S, D, maxlen, torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        _lib.check(rc, "ll_suffix_prologue")
+    if st.get("dyn") is None:
+        rc = st["lib"].ll_suffix_prologue(posid.data_ptr(), self.rotary_emb.inv_freq.data_ptr(), float(self.rotary_emb.attention_scaling),
+                                          attention_mask.data_ptr(), attention_mask.stride(0), clayers[0].cumulative_length.data_ptr(),
+                                          cos.data_ptr(), sin.data_ptr(), mask.data_ptr(), B, S, D, maxlen, torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            _lib.check(rc, "ll_suffix_prologue")
+    else:
+        inv0, table, rows = _dyn_freqs(self, st, maxlen)
+        rc = st["lib"].ll_suffix_prologue_dyn(posid.data_ptr(), inv0.data_ptr(), table.data_ptr() if table is not None else None,
+                                              st["dyn"]["max_pos"], rows, 1.0, attention_mask.data_ptr(), attention_mask.stride(0),
+                                              clayers[0].cumulative_length.data_ptr(), cos.data_ptr(), sin.data_ptr(), mask.data_ptr(), B, S, D,
+                                              maxlen, torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            _lib.check(rc, "ll_suffix_prologue_dyn")
     for layer in layers:
         h = layer._ll_fused.run_suffix(h, mask, cache, (cos, sin), B, S)
     h = self.norm(h)
@@ -955,21 +979,60 @@ def suffix_on_fused_layers(model: nn.Module, on: bool) -> bool:
     return True
 
 
-def fuse_model_decode(model: nn.Module) -> bool:
-    """Run the base model's decode step without HF's per-token mask / rotary-table construction (call after
-    ``fuse_decoder_layers``; needs every layer fused, default rope, f32 ``inv_freq``).  Returns whether it was installed."""
+def _dyn_freqs(base, st, maxlen: int):
+    """(inv_freq0, table or None, table rows) of a dynamic NTK model for a static cache of ``maxlen`` slots; the table (rope.py) is built
+    once per cache length -- in the eager warm-up step that precedes every capture -- and kept with the patch."""
+    dyn = st["dyn"]
+    rot = base.rotary_emb
+    if maxlen not in dyn["tables"]:
+        dyn["tables"][maxlen] = dynamic_inv_freq_table(rot.config, rot.original_inv_freq.device, maxlen)
+    table = dyn["tables"][maxlen]
+    return rot.original_inv_freq, table, 0 if table is None else table.shape[0]
+
+
+def model_decode_declined(model: nn.Module) -> Optional[str]:
+    """Why ``fuse_model_decode`` would not install on this model (None: it would).  Rotary types: default and the ones with constants fixed at
+    construction (linear, llama3, yarn) run on the existing prologue, dynamic NTK on its device-side form; longrope, proportional and
+    modules with per-layer-type tables stay on HF's module."""
     base = getattr(model, "model", model)
     layers = getattr(base, "layers", None)
     rot = getattr(base, "rotary_emb", None)
-    if (layers is None or rot is None or hasattr(base, "_ll_decode") or not all(hasattr(l, "_ll_fused") for l in layers)
-            or not hasattr(rot, "inv_freq") or rot.inv_freq.dtype != torch.float32 or not rot.inv_freq.is_cuda
-            or getattr(rot, "rope_type", "default") != "default" or not hasattr(base, "embed_tokens") or not hasattr(base, "norm")
-            or getattr(base, "has_sliding_layers", False)):
+    if layers is None or rot is None or not hasattr(base, "embed_tokens") or not hasattr(base, "norm"):
+        return "not a Llama-layout base model"
+    if hasattr(base, "_ll_decode"):
+        return "already installed"
+    if not all(hasattr(l, "_ll_fused") for l in layers):
+        return "not every decoder layer is fused"
+    rope_type = getattr(rot, "rope_type", "default")
+    if not isinstance(rope_type, str):
+        return "rope_type per layer type"
+    if rope_type not in STATIC_ROPE_TYPES and rope_type != "dynamic":
+        return f"rope_type={rope_type}"
+    if not hasattr(rot, "inv_freq") or rot.inv_freq.dtype != torch.float32 or not rot.inv_freq.is_cuda:
+        return "inv_freq is not an f32 device tensor"
+    if getattr(base, "has_sliding_layers", False):
+        return "sliding-window layers"
+    if rot.inv_freq.numel() * 2 != layers[0]._ll_fused.D:
+        return "partial rotary dimension"
+    if rope_type == "dynamic":
+        inv0 = getattr(rot, "original_inv_freq", None)
+        if (inv0 is None or inv0.dtype != torch.float32 or not inv0.is_cuda or inv0.shape != rot.inv_freq.shape
+                or not getattr(getattr(rot, "config", None), "max_position_embeddings", None)):
+            return "dynamic rope without an f32 device original_inv_freq"
+    return None
+
+
+def fuse_model_decode(model: nn.Module) -> bool:
+    """Run the base model's decode step without HF's per-token mask / rotary-table construction (call after
+    ``fuse_decoder_layers``; needs every layer fused, f32 ``inv_freq`` and a rope type of ``model_decode_declined``'s list: default,
+    linear, llama3, yarn, dynamic).  Returns whether it was installed."""
+    if model_decode_declined(model) is not None:
         return False
-    D = layers[0]._ll_fused.D
-    if rot.inv_freq.numel() * 2 != D:
-        return False
-    base._ll_decode = {"lib": _lib.load(), "D": D}
+    base = getattr(model, "model", model)
+    rot = base.rotary_emb
+    base._ll_decode = {"lib": _lib.load(), "D": base.layers[0]._ll_fused.D}
+    if rot.rope_type == "dynamic":
+        base._ll_decode["dyn"] = {"max_pos": int(rot.config.max_position_embeddings), "tables": {}}
     base._ll_model_orig = base.forward
     base.forward = types.MethodType(_model_forward, base)
     return True
@@ -1022,7 +1085,10 @@ def accelerate_llm(model: nn.Module, linears: bool = True, fuse: bool = True, la
         if info["decode_attention"] and layers:
             info["decoder_layers_5_launches"] = fuse_decoder_layers(model)
             if model_decode:
+                declined = model_decode_declined(model)
                 info["decode_prologue_1_launch"] = fuse_model_decode(model)
+                if not info["decode_prologue_1_launch"]:
+                    info["decode_prologue_declined"] = declined
     if bits is not None:
         base = getattr(model, "model", model)
         fused = [l.__dict__.get("_ll_fused") for l in (getattr(base, "layers", None) or [])]

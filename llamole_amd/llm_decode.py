@@ -139,6 +139,72 @@ class GraphedDecoder:
         self._cache_fused = False
         self._key = None
         self._graph = None
+        self._eager_keys = set()        # (batch, cache length) shapes whose step is not captured (_warm_up)
+
+    def _host_read_rope(self):
+        """The model's rope type when its rotary module reads the position ids on the host (dynamic NTK, longrope: transformers
+        dynamic_rope_update), else None.  Such a forward cannot be captured: the host read raises inside a capture, and a replay would keep
+        the frequency tensor of the capture."""
+        from .rope import HOST_READ_ROPE_TYPES, rope_type_of
+        rope_type = rope_type_of(self.model)
+        return rope_type if isinstance(rope_type, str) and rope_type in HOST_READ_ROPE_TYPES else None
+
+    def _served_by_fused_prologue(self) -> bool:
+        """Whether the last forward of the base model ran on the fused decode (llm_accel._model_forward), which picks a dynamic model's
+        frequencies on the device and never calls HF's rotary module."""
+        base = getattr(self.model, "model", self.model)
+        return bool(base.__dict__.get("_ll_decode", {}).get("served"))
+
+    def _graphs_off(self, rope_type: str, why: str):
+        """For good: the reason (what is installed on the model, how this decoder was built) holds for every later call."""
+        import warnings
+        warnings.warn(f"rope_type={rope_type} reads the position ids on the host and {why}: this decoder runs eagerly (no hipGraph) "
+                      "from now on")
+        self.use_graph = self.graph_suffix = False
+        self._graph = self._beam_graph = None
+        self._side_graphs = {}
+
+    def _graph_on(self) -> bool:
+        """Whether the decode step of the current (batch, cache length) shape is replayed as a graph."""
+        return self.use_graph and self._key not in self._eager_keys
+
+    def _before_prefill(self):
+        """A dynamic NTK module is put back to its constructed state before each prefill: a call's result then does not depend on the
+        lengths of earlier calls, and prefill (HF's eager module) and decode (the fused prologue) agree.  A model whose rotary module reads
+        the device on the host is captured only when the fused prologue serves its decode step; where that is known not to be the case
+        before the first step -- the prologue is not installed, or this decoder does not use the fused cache append the prologue needs --
+        the decoder turns its graphs off here, everything else is decided after the eager warm-up step (_warm_up)."""
+        rope_type = self._host_read_rope()
+        if rope_type is None:
+            return
+        from .rope import reset_dynamic_rope
+        reset_dynamic_rope(self.model)
+        base = getattr(self.model, "model", self.model)
+        if (self.use_graph or self.graph_suffix) and ("_ll_decode" not in base.__dict__ or not self.fused_cache):
+            self._graphs_off(rope_type, "the fused decode prologue is not installed" if "_ll_decode" not in base.__dict__
+                             else "this decoder runs without the fused cache append that the fused prologue needs")
+
+    def _warm_up(self):
+        """The eager step on a side stream that precedes the capture of the decode step (its state is rewound).  For a rotary module that
+        reads the device on the host this is also where the capture is decided: if the step was not served by the fused prologue (more
+        rows than it takes, a layer that is not eligible at this shape, an embedding that is not bf16) HF's module ran, and the decoder
+        runs this (batch, cache length) shape eagerly from then on (one warning per shape) instead of entering a capture with a host read
+        inside; calls at shapes the prologue serves stay graphed."""
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            self._step()
+            # the warm-up advanced the cache's on-device length counters; rewind them so that the captured step (replayed for this same
+            # token) writes the same slot again
+            self._rewind(self.tok.shape[1])
+        torch.cuda.current_stream().wait_stream(s)
+        rope_type = self._host_read_rope()
+        if rope_type is not None and not self._served_by_fused_prologue():
+            import warnings
+            warnings.warn(f"rope_type={rope_type} reads the position ids on the host and the fused decode prologue does not serve this "
+                          f"model's step at {self.tok.shape[0]} rows: calls of this shape run eagerly (no hipGraph)")
+            self._eager_keys.add(self._key)
+            self._graph = self._beam_graph = None
 
     # static buffers + captured step for a (batch, max_len) shape
     def _prepare(self, B: int, max_len: int, device, use_embeds: bool):
@@ -246,11 +312,14 @@ class GraphedDecoder:
 
         from .llm_accel import suffix_on_fused_layers
         fused = self._cache_fused and os.environ.get("LLAMOLE_FUSED_SUFFIX", "1") != "0" and suffix_on_fused_layers(self.model, True)
+        key = ("suffix", B, S)
         try:
-            hidden = self._captured(("suffix", B, S), [(torch.empty_like, tail_ids), (torch.empty_like, pos), (torch.empty_like, posid)], fwd)
+            hidden = self._captured(key, [(torch.empty_like, tail_ids), (torch.empty_like, pos), (torch.empty_like, posid)], fwd)
         finally:
             if fused:
                 suffix_on_fused_layers(self.model, False)
+        if self._side_graphs.get(key) == "seen" and self._host_read_rope() is not None and not self._served_by_fused_prologue():
+            self._side_graphs[key] = "eager"        # the eager first call ran HF's rotary module (a host read): this shape is never captured
         if self._cache_fused:
             self.cache.layers[0].cumulative_length.add_(S)
         return hidden
@@ -325,14 +394,10 @@ class GraphedDecoder:
                 if bool(self.done.all()):
                     break
                 mark("generate: rendezvous")
-            if self.use_graph:
+            if self._graph_on() and self._graph is None:
+                self._warm_up()                                   # the forward only, state rewound; may turn this shape's graph off
+            if self._graph_on():
                 if self._graph is None:
-                    s = torch.cuda.Stream()
-                    s.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(s):
-                        self._step()                              # warm-up of the forward only; state rewound below
-                        self._rewind(self.tok.shape[1])
-                    torch.cuda.current_stream().wait_stream(s)
                     self._graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(self._graph, capture_error_mode="thread_local"):
                         self.logits = self._step()
@@ -378,6 +443,7 @@ class GraphedDecoder:
         refresh_weight_copies(self.model)       # concatenated / converted weight copies follow their sources (in place)
         ref = input_ids if input_ids is not None else inputs_embeds
         B, P = ref.shape[0], ref.shape[1]
+        self._before_prefill()
         device = ref.device
         if attention_mask is None:
             attention_mask = torch.ones(B, P, dtype=torch.long, device=device)
@@ -455,17 +521,11 @@ class GraphedDecoder:
             self.pos.fill_(P + t)
             if t > 0:
                 self.posid.add_(1)
-            if self.use_graph:
+            if self._graph_on() and self._graph is None:
+                self._warm_up()                                   # on a side stream, state rewound; may turn this shape's graph off
+            if self._graph_on():
                 if self._graph is None:
-                    # warm-up on a side stream, then capture the stock HF forward once
-                    s = torch.cuda.Stream()
-                    s.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(s):
-                        self._step()
-                        # the warm-up advanced the cache's on-device length counters; rewind them so that the
-                        # captured step (replayed below for this same token) writes the same slot again
-                        self._rewind(self.tok.shape[1])
-                    torch.cuda.current_stream().wait_stream(s)
+                    # capture the forward once
                     self._graph = torch.cuda.CUDAGraph()
                     # thread-local capture: a RCCL watchdog thread polling events must not invalidate the capture
                     with torch.cuda.graph(self._graph, capture_error_mode="thread_local"):
@@ -544,6 +604,7 @@ class GraphedDecoder:
         refresh_weight_copies(self.model)
         ref = input_ids if input_ids is not None else inputs_embeds
         B, P = ref.shape[0], ref.shape[1]
+        self._before_prefill()
         device = ref.device
         if attention_mask is None:
             attention_mask = torch.ones(B, P, dtype=torch.long, device=device)
@@ -622,14 +683,10 @@ class GraphedDecoder:
                 self.pos.fill_(P + t - 1)
                 if t > 1:
                     self.posid.add_(1)
-            if self.use_graph:
+            if self._graph_on() and self._beam_graph is None:
+                self._warm_up()                                   # the forward only, state rewound; may turn this shape's graph off
+            if self._graph_on():
                 if self._beam_graph is None:
-                    s = torch.cuda.Stream()
-                    s.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(s):
-                        self._step()                              # warm-up of the forward only; state rewound below
-                        self._rewind(self.tok.shape[1])
-                    torch.cuda.current_stream().wait_stream(s)
                     self._beam_graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(self._beam_graph, capture_error_mode="thread_local"):
                         self._beam_logits = self._step()

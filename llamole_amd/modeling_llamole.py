@@ -97,6 +97,21 @@ class GraphLLMForCausalMLM(nn.Module):
         return self.language_model.generate(inputs=inputs, attention_mask=attention_mask, **kwargs)
 
     # ------------------------------------------------------------------ construction
+    @staticmethod
+    def load_language_model(model_args, data_args=None, training_args=None):
+        """The stock HF causal LM of ``model_name_or_path`` in the compute dtype (on the CPU; ``from_pretrained`` moves it).  ``rope_scaling:
+        linear | dynamic`` of the YAML is applied to its config before the weights are loaded, with model_max_length = cutoff_len (reference
+        model_utils/rope.py, hparams/parser.py:303)."""
+        from transformers import AutoConfig, AutoModelForCausalLM
+        from .rope import check_rope_scaling, configure_rope
+        compute_dtype = getattr(model_args, "compute_dtype", torch.bfloat16)
+        rope_scaling = check_rope_scaling(getattr(model_args, "rope_scaling", None))
+        if rope_scaling is None:
+            return AutoModelForCausalLM.from_pretrained(model_args.model_name_or_path, torch_dtype=compute_dtype)
+        config = AutoConfig.from_pretrained(model_args.model_name_or_path)
+        configure_rope(config, rope_scaling, getattr(data_args, "cutoff_len", None), is_trainable=bool(getattr(training_args, "do_train", False)))
+        return AutoModelForCausalLM.from_pretrained(model_args.model_name_or_path, config=config, torch_dtype=compute_dtype)
+
     @classmethod
     def from_pretrained(cls, tokenizer, model_args, data_args, training_args, finetuning_args, load_adapter=False,
                         add_valuehead=False, language_model=None):
@@ -111,8 +126,7 @@ class GraphLLMForCausalMLM(nn.Module):
             if len(apath) != 1:
                 raise ValueError("Only one adapter is supported at a time.")
         if language_model is None:
-            from transformers import AutoModelForCausalLM
-            language_model = AutoModelForCausalLM.from_pretrained(model_args.model_name_or_path, torch_dtype=compute_dtype)
+            language_model = cls.load_language_model(model_args, data_args, training_args)
             if len(tokenizer) > language_model.get_input_embeddings().weight.shape[0]:
                 language_model.resize_token_embeddings(len(tokenizer))
             if load_adapter:

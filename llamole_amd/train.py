@@ -4,7 +4,8 @@ reference ``src/train/mmsft/workflow.py:41-118`` as a thin loop around ``sft.sft
 Reads the keys of ``config/train/mistral_lora.yaml`` (model_name_or_path, new_special_tokens, graph_*_path, graph_lm_connector_path,
 finetuning_type lora, lora_target, lora_rank, lora_alpha, learned_query_size, dataset, dataset_dir, cutoff_len, output_dir,
 logging_steps, save_steps, per_device_train_batch_size, gradient_accumulation_steps, learning_rate, num_train_epochs, max_steps,
-lr_scheduler_type cosine, warmup_ratio, bf16 / pure_bf16, loss_weight_{lm,design,retro}, resume_from_checkpoint / adapter_name_or_path).
+lr_scheduler_type cosine, warmup_ratio, bf16 / pure_bf16, loss_weight_{lm,design,retro}, resume_from_checkpoint / adapter_name_or_path,
+rope_scaling linear | dynamic -- applied to the LLM config with model_max_length = cutoff_len; dynamic warns, as in the reference).
 
 What it is: data-parallel SFT, one process per GPU (``torch.distributed`` "nccl" = RCCL over xGMI; bucketed direct all-reduce of the
 adapter + connector gradients, ``distributed.allreduce_gradients``), LoRA on the HF language model (``sft.add_lora``; peft is not in this
