@@ -229,7 +229,8 @@ int ll_silu_mul_bf16(const void *gate, const void *up, void *out, int rows, int 
 /* ll_kv_append_bf16 : StaticCache layer update at decode: write k_new/v_new [B,nkv,S,D] (element strides of dims 0..2) into
  *                     keys/values [B,nkv,maxlen,D] at positions *pos .. *pos+S-1 (pos: device int64).
  * ll_decode_attn_bf16: softmax(q K^T * scale + mask) V over the static cache with grouped-query heads; q [B,nh,S,D] strided,
- *                     mask bool [B,1,S,maxlen] (strides of dims 0 and 2), out [B,S,nh,D] contiguous; D in {64,128}. */
+ *                     mask bool [B,1,S,maxlen] (strides of dims 0 and 2), out [B,S,nh,D] contiguous; D in {64,128}, maxlen <= 16384
+ *                     (LL_EINVAL beyond: a workgroup keeps the scores of all keys in LDS).  A query row without a visible key gives zeros. */
 int ll_kv_append_bf16(void *K, void *V, const void *k_new, const void *v_new, const int64_t *pos, int B, int nkv, int S,
                       int maxlen, int D, const int64_t *kstr, const int64_t *vstr, void *stream);
 int ll_decode_attn_bf16(const void *q, const void *K, const void *V, const void *mask, void *out, int B, int nh, int nkv, int S,
@@ -247,7 +248,8 @@ int ll_decode_attn_bf16(const void *q, const void *K, const void *V, const void 
  *     qkv [B, (nh+2*nkv)*D] rows (stride ld_qkv) = fused q|k|v projection; cos/sin [B or 1, D] (batch stride cs_stride, 0 to
  *     broadcast); Kc/Vc [B,nkv,maxlen,D] static cache, appended at *pos (device int64); mask bool [B,maxlen] rows
  *     (stride mask_stride) for the new query (causal decode: cache slots behind *pos hold no keys yet and must be masked -- with more than 16
- *     sequences, where one workgroup serves the whole KV group, they are not even fetched); out [B, nh*D].  D in {64,128}.
+ *     sequences, where one workgroup serves the whole KV group, they are not even fetched); out [B, nh*D].  D in {64,128},
+ *     maxlen <= 16384 (LL_EINVAL beyond).
  * (timing / tuning hooks of these kernels: include/llamole_hip_tuning.h) */
 #define LL_GEMV_PLAIN 0
 #define LL_GEMV_RESIDUAL 1
@@ -269,7 +271,8 @@ int ll_decode_prologue(const int64_t *position_ids, const float *inv_freq, float
  *     *pos .. *pos+S-1.  Rows r = b*S + s.  Prologue: cos/sin [B*S,D] for position_ids [B*S], key mask [B*S,maxlen]: key j visible to row
  *     (b,s) iff j <= *pos + s and mask2d[b][j] != 0.  Attention: qkv [B*S, (nh+2*nkv)*D] (row stride ld_qkv); rotary on q and k, the
  *     new keys / values stored to Kc/Vc [B,nkv,maxlen,D], softmax(q K^T * scale + mask) V over the cache -> out [B*S, nh*D]; bit for
- *     bit ll_rope_bf16 + ll_kv_append_bf16 + ll_decode_attn_bf16.  S <= 16, D in {64,128}. */
+ *     bit ll_rope_bf16 + ll_kv_append_bf16 + ll_decode_attn_bf16.  S <= 16, D in {64,128}, maxlen <= 16384 (LL_EINVAL beyond); rows whose
+ *     slot *pos + s lies past the cache are not stored (ll_kv_append_bf16 drops them alike). */
 int ll_suffix_prologue(const int64_t *position_ids, const float *inv_freq, float attention_scaling, const int64_t *mask2d,
                        int64_t mask_stride, const int64_t *pos, void *cos, void *sin, void *mask_out, int B, int S, int D, int maxlen,
                        void *stream);

@@ -791,14 +791,19 @@ int ll_decode_attn_rope_bf16(const void *qkv, int64_t ld_qkv, const void *cos, c
     }
     const size_t lds = (size_t)(D + ATTN_PART_FLOATS) * 4 + (size_t)2 * D * 2 + (size_t)maxlen * 4;
     dim3 grid(nh, B);
-    if (D == 128)
-        hipLaunchKernelGGL((decode_attn_rope_kernel<128>), grid, dim3(ATTN_THREADS), lds, (hipStream_t)stream, (const bf16_t *)qkv, ld_qkv,
-                           (const bf16_t *)cos, (const bf16_t *)sin, cs_stride, (bf16_t *)Kc, (bf16_t *)Vc, (const long long *)pos,
-                           (const unsigned char *)mask, mask_stride, (bf16_t *)out, nh, nkv, maxlen, scale);
-    else
-        hipLaunchKernelGGL((decode_attn_rope_kernel<64>), grid, dim3(ATTN_THREADS), lds, (hipStream_t)stream, (const bf16_t *)qkv, ld_qkv,
-                           (const bf16_t *)cos, (const bf16_t *)sin, cs_stride, (bf16_t *)Kc, (bf16_t *)Vc, (const long long *)pos,
-                           (const unsigned char *)mask, mask_stride, (bf16_t *)out, nh, nkv, maxlen, scale);
+#define LL_ATTN(D_)                                                                                                                      \
+    do {                                                                                                                                 \
+        static size_t attr = 64 * 1024;       /* > 64 KB of dynamic LDS (maxlen > ~12 k keys) needs the attribute */                    \
+        if (lds > attr) {                                                                                                                \
+            LL_HIP(hipFuncSetAttribute((const void *)decode_attn_rope_kernel<D_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            attr = lds;                                                                                                                  \
+        }                                                                                                                                \
+        hipLaunchKernelGGL((decode_attn_rope_kernel<D_>), grid, dim3(ATTN_THREADS), lds, (hipStream_t)stream, (const bf16_t *)qkv,       \
+                           ld_qkv, (const bf16_t *)cos, (const bf16_t *)sin, cs_stride, (bf16_t *)Kc, (bf16_t *)Vc,                      \
+                           (const long long *)pos, (const unsigned char *)mask, mask_stride, (bf16_t *)out, nh, nkv, maxlen, scale);    \
+    } while (0)
+    if (D == 128) LL_ATTN(128); else LL_ATTN(64);
+#undef LL_ATTN
     LL_LAUNCH_CHECK();
     return LL_OK;
 }
@@ -864,14 +869,19 @@ int ll_suffix_attn_rope_bf16(const void *qkv, int64_t ld_qkv, const void *cos, c
              "ll_suffix_attn_rope_bf16: unsupported shape");
     const size_t lds = ((size_t)maxlen + D + ATTN_PART_FLOATS) * 4;
     dim3 grid(nh, B * S);
-    if (D == 128)
-        hipLaunchKernelGGL((suffix_attn_rope_kernel<128>), grid, dim3(ATTN_THREADS), lds, (hipStream_t)stream, (const bf16_t *)qkv, ld_qkv,
-                           (const bf16_t *)cos, (const bf16_t *)sin, (bf16_t *)Kc, (bf16_t *)Vc, (const long long *)pos,
-                           (const unsigned char *)mask, (bf16_t *)out, nh, nkv, S, maxlen, scale);
-    else
-        hipLaunchKernelGGL((suffix_attn_rope_kernel<64>), grid, dim3(ATTN_THREADS), lds, (hipStream_t)stream, (const bf16_t *)qkv, ld_qkv,
-                           (const bf16_t *)cos, (const bf16_t *)sin, (bf16_t *)Kc, (bf16_t *)Vc, (const long long *)pos,
-                           (const unsigned char *)mask, (bf16_t *)out, nh, nkv, S, maxlen, scale);
+#define LL_ATTN(D_)                                                                                                                      \
+    do {                                                                                                                                 \
+        static size_t attr = 64 * 1024;       /* > 64 KB of dynamic LDS (maxlen > ~12 k keys) needs the attribute */                    \
+        if (lds > attr) {                                                                                                                \
+            LL_HIP(hipFuncSetAttribute((const void *)suffix_attn_rope_kernel<D_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            attr = lds;                                                                                                                  \
+        }                                                                                                                                \
+        hipLaunchKernelGGL((suffix_attn_rope_kernel<D_>), grid, dim3(ATTN_THREADS), lds, (hipStream_t)stream, (const bf16_t *)qkv,       \
+                           ld_qkv, (const bf16_t *)cos, (const bf16_t *)sin, (bf16_t *)Kc, (bf16_t *)Vc, (const long long *)pos,         \
+                           (const unsigned char *)mask, (bf16_t *)out, nh, nkv, S, maxlen, scale);                                      \
+    } while (0)
+    if (D == 128) LL_ATTN(128); else LL_ATTN(64);
+#undef LL_ATTN
     LL_LAUNCH_CHECK();
     return LL_OK;
 }

@@ -212,14 +212,19 @@ int ll_decode_attn_bf16(const void *q, const void *K, const void *V, const void 
     LL_CHECK((D == 64 || D == 128) && nh % nkv == 0 && maxlen >= 1 && maxlen <= 16384, "ll_decode_attn_bf16: unsupported shape");
     const size_t lds = ((size_t)maxlen + D + ATTN_PART_FLOATS) * 4;
     dim3 grid(nh, B * S);
-    if (D == 128)
-        hipLaunchKernelGGL((decode_attn_bf16_kernel<128>), grid, dim3(ATTN_THREADS), lds, (hipStream_t)stream, (const bf16_t *)q,
-                           (const bf16_t *)K, (const bf16_t *)V, (const unsigned char *)mask, (bf16_t *)out, nh, nkv, S, maxlen,
-                           scale, qstr[0], qstr[1], qstr[2], mstr[0], mstr[1]);
-    else
-        hipLaunchKernelGGL((decode_attn_bf16_kernel<64>), grid, dim3(ATTN_THREADS), lds, (hipStream_t)stream, (const bf16_t *)q,
-                           (const bf16_t *)K, (const bf16_t *)V, (const unsigned char *)mask, (bf16_t *)out, nh, nkv, S, maxlen,
-                           scale, qstr[0], qstr[1], qstr[2], mstr[0], mstr[1]);
+#define LL_ATTN(D_)                                                                                                                      \
+    do {                                                                                                                                 \
+        static size_t attr = 64 * 1024;       /* > 64 KB of dynamic LDS (maxlen > ~12 k keys) needs the attribute */                    \
+        if (lds > attr) {                                                                                                                \
+            LL_HIP(hipFuncSetAttribute((const void *)decode_attn_bf16_kernel<D_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            attr = lds;                                                                                                                  \
+        }                                                                                                                                \
+        hipLaunchKernelGGL((decode_attn_bf16_kernel<D_>), grid, dim3(ATTN_THREADS), lds, (hipStream_t)stream, (const bf16_t *)q,         \
+                           (const bf16_t *)K, (const bf16_t *)V, (const unsigned char *)mask, (bf16_t *)out, nh, nkv, S, maxlen, scale,  \
+                           qstr[0], qstr[1], qstr[2], mstr[0], mstr[1]);                                                                 \
+    } while (0)
+    if (D == 128) LL_ATTN(128); else LL_ATTN(64);
+#undef LL_ATTN
     LL_LAUNCH_CHECK();
     return LL_OK;
 }
