@@ -250,6 +250,13 @@ int ll_decode_attn_bf16(const void *q, const void *K, const void *V, const void 
  *     (stride mask_stride) for the new query (causal decode: cache slots behind *pos hold no keys yet and must be masked -- with more than 16
  *     sequences, where one workgroup serves the whole KV group, they are not even fetched); out [B, nh*D].  D in {64,128},
  *     maxlen <= 16384 (LL_EINVAL beyond).
+ * ll_decode_attn_rope_qkn_bf16 : the same for the Qwen3 layout, whose attention normalises every q head row and every k head row over
+ *     head_dim (Qwen3RMSNorm q_norm / k_norm, transformers modeling_qwen3.py) between the projection and the rotary embedding.  Per head
+ *     row x [D] of q (weights q_norm_w [D] bf16) and of k (k_norm_w [D] bf16), one eps for both:
+ *         xh = bf16( x * rsqrt( mean_D(x^2) + eps ) )        mean, rsqrt and product in f32, ONE rounding to bf16
+ *         y  = bf16( w * xh )                                f32 product of two bf16 values, ONE rounding to bf16
+ *     and y takes the place of x in the rotary arithmetic above; v is not normalised.  Same choice between the per-head and the grouped
+ *     kernel, same shape bounds.  NULL norm weights or eps <= 0: LL_EINVAL, nothing is launched.
  * (timing / tuning hooks of these kernels: include/llamole_hip_tuning.h) */
 #define LL_GEMV_PLAIN 0
 #define LL_GEMV_RESIDUAL 1
@@ -259,6 +266,10 @@ int ll_gemv_fused_bf16(const void *x, int ldx, const void *W, int ldw, const flo
 int ll_decode_attn_rope_bf16(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, int64_t cs_stride, void *Kc,
                              void *Vc, const int64_t *pos, const void *mask, int64_t mask_stride, void *out, int B, int nh,
                              int nkv, int maxlen, int D, float scale, void *stream);
+int ll_decode_attn_rope_qkn_bf16(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, int64_t cs_stride, void *Kc,
+                                 void *Vc, const int64_t *pos, const void *mask, int64_t mask_stride, void *out, int B, int nh,
+                                 int nkv, int maxlen, int D, float scale, const void *q_norm_w, const void *k_norm_w, float eps,
+                                 void *stream);
 /* ll_decode_prologue : per-token prologue of a decode step in one launch: cos/sin [B,D] bf16 of Qwen2RotaryEmbedding.forward
  *     (transformers modeling_qwen2.py: inv_freq * position in f32, cos/sin, * attention_scaling, cast) for position_ids [B],
  *     and the boolean key mask [B,maxlen] of create_causal_mask (masking_utils.py) for one new query at cache slot *pos:
@@ -272,12 +283,18 @@ int ll_decode_prologue(const int64_t *position_ids, const float *inv_freq, float
  *     (b,s) iff j <= *pos + s and mask2d[b][j] != 0.  Attention: qkv [B*S, (nh+2*nkv)*D] (row stride ld_qkv); rotary on q and k, the
  *     new keys / values stored to Kc/Vc [B,nkv,maxlen,D], softmax(q K^T * scale + mask) V over the cache -> out [B*S, nh*D]; bit for
  *     bit ll_rope_bf16 + ll_kv_append_bf16 + ll_decode_attn_bf16.  S <= 16, D in {64,128}, maxlen <= 16384 (LL_EINVAL beyond); rows whose
- *     slot *pos + s lies past the cache are not stored (ll_kv_append_bf16 drops them alike). */
+ *     slot *pos + s lies past the cache are not stored (ll_kv_append_bf16 drops them alike).
+ *     ll_suffix_attn_rope_qkn_bf16 : ll_suffix_attn_rope_bf16 with the per-head q / k RMSNorm of ll_decode_attn_rope_qkn_bf16 (same formula, same
+ *     two roundings, same device function) in front of the rotation of every q row and every new k row: a key it stores is bit for bit the key
+ *     ll_decode_attn_rope_qkn_bf16 stores for the same row and position.  NULL norm weights or eps <= 0: LL_EINVAL, nothing is launched. */
 int ll_suffix_prologue(const int64_t *position_ids, const float *inv_freq, float attention_scaling, const int64_t *mask2d,
                        int64_t mask_stride, const int64_t *pos, void *cos, void *sin, void *mask_out, int B, int S, int D, int maxlen,
                        void *stream);
 int ll_suffix_attn_rope_bf16(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, void *Kc, void *Vc, const int64_t *pos,
                              const void *mask, void *out, int B, int S, int nh, int nkv, int maxlen, int D, float scale, void *stream);
+int ll_suffix_attn_rope_qkn_bf16(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, void *Kc, void *Vc, const int64_t *pos,
+                                 const void *mask, void *out, int B, int S, int nh, int nkv, int maxlen, int D, float scale,
+                                 const void *q_norm_w, const void *k_norm_w, float eps, void *stream);
 /* ll_decode_prologue_dyn / ll_suffix_prologue_dyn : the two prologues for dynamic NTK rope (transformers dynamic_rope_update) without its
  *     host read of the position ids.  With L = max(position_ids of the call) + 1, read on the device by every workgroup, the frequencies are
  *     inv_freq0 [D/2] (the module's constructed original_inv_freq) while L <= max_pos (= config.max_position_embeddings) and row

@@ -271,17 +271,42 @@ __global__ __launch_bounds__(256) void gemv_stage_kernel(const bf16_t *__restric
     }
 }
 
+// Per-head q/k RMSNorm of the Qwen3 layout (Qwen3RMSNorm over head_dim, between the projection and the rotary embedding), on the pair of
+// elements (lane, lane + D/2) a rotating lane holds:  xh = bf16(x * rsqrt(mean_D(x^2) + eps)),  y = bf16(w * xh)  -- f32 arithmetic, each product
+// rounded to bf16 once, as the module computes on bf16 data.  The whole head row sits in one wave, so the mean is one wave_sum and no LDS.
+// QKN: called by ALL 64 lanes of the wave (D = 64: lanes 32..63 contribute zeros and get zeros back).  Without QKN it is the plain load of the
+// pair, called by the lanes < D/2 only, where the kernels always loaded it.
+template <int D, bool QKN>
+__device__ __forceinline__ void head_pair(const bf16_t *src, const bf16_t *nw, float eps, int lane, float &x1, float &x2) {
+    constexpr int half = D / 2;
+    if (!QKN) {
+        x1 = bf16_to_f32(src[lane]);
+        x2 = bf16_to_f32(src[lane + half]);
+        return;
+    }
+    const bool on = lane < half;
+    x1 = on ? bf16_to_f32(src[lane]) : 0.f;
+    x2 = on ? bf16_to_f32(src[lane + half]) : 0.f;
+    const float w1 = on ? bf16_to_f32(nw[lane]) : 0.f, w2 = on ? bf16_to_f32(nw[lane + half]) : 0.f;
+    const float ss = wave_sum(x1 * x1 + x2 * x2);
+    const float rstd = rsqrtf(ss / (float)D + eps);
+    x1 = bfr2(w1 * bfr2(x1 * rstd));
+    x2 = bfr2(w2 * bfr2(x2 * rstd));
+}
+
 // Rotary embedding + KV append + GQA decode attention for ONE new position per sequence.
 // grid (nh, B).  qkv row b = [q: nh*D | k: nkv*D | v: nkv*D] (output of the fused q/k/v GEMV).  The new key / value of
 // the head's KV group is rotated in LDS and used from there; the first query head of each group also stores it to the
 // cache at *pos.  Nobody reads cache slot *pos in this launch, so there is no cross-workgroup dependency.
-template <int D>
+// QKN: every q head row and the k head row pass head_pair's RMSNorm (weights qnw / knw, one eps) before the rotation; v does not.
+template <int D, bool QKN>
 __global__ __launch_bounds__(ATTN_THREADS) void decode_attn_rope_kernel(const bf16_t *__restrict__ qkv, int64_t ld_qkv,
                                                                const bf16_t *__restrict__ cs, const bf16_t *__restrict__ sn,
                                                                int64_t cs0, bf16_t *__restrict__ K, bf16_t *__restrict__ V,
                                                                const long long *__restrict__ pos_ptr,
                                                                const unsigned char *__restrict__ mask, int64_t ms0,
-                                                               bf16_t *__restrict__ out, int nh, int nkv, int maxlen, float scale) {
+                                                               bf16_t *__restrict__ out, int nh, int nkv, int maxlen, float scale,
+                                                               const bf16_t *__restrict__ qnw, const bf16_t *__restrict__ knw, float eps) {
     extern __shared__ __attribute__((aligned(16))) float sm_attn2[];
     float *qs = sm_attn2;                 // [D]     rotated query, f32 of its bf16 value
     float *part = qs + D;                 // [waves][rows per load][D] partial outputs = ATTN_PART_FLOATS for either D
@@ -303,18 +328,20 @@ __global__ __launch_bounds__(ATTN_THREADS) void decode_attn_rope_kernel(const bf
     AttnTile0<D> t0;      // first 256 keys / values / mask bytes: requested before the rotary arithmetic
     attn_prefetch<D>(t0, Kb, Vb, mrow, maxlen, tid, lane, wave);
     if (wave == 0) {
+        float x1, x2;
+        if (QKN) head_pair<D, true>(row + h * D, qnw, eps, lane, x1, x2);
         if (lane < half) {
-            const bf16_t *src = row + h * D;
-            const float x1 = bf16_to_f32(src[lane]), x2 = bf16_to_f32(src[lane + half]);
+            if (!QKN) head_pair<D, false>(row + h * D, qnw, eps, lane, x1, x2);
             const float c1 = bf16_to_f32(c[lane]), c2 = bf16_to_f32(c[lane + half]);
             const float s1 = bf16_to_f32(sv[lane]), s2 = bf16_to_f32(sv[lane + half]);
             qs[lane] = bfr2(bfr2(x1 * c1) + bfr2(-x2 * s1));
             qs[lane + half] = bfr2(bfr2(x2 * c2) + bfr2(x1 * s2));
         }
     } else if (wave == 1) {
+        float x1, x2;
+        if (QKN) head_pair<D, true>(row + (nh + kvh) * D, knw, eps, lane, x1, x2);
         if (lane < half) {
-            const bf16_t *src = row + (nh + kvh) * D;
-            const float x1 = bf16_to_f32(src[lane]), x2 = bf16_to_f32(src[lane + half]);
+            if (!QKN) head_pair<D, false>(row + (nh + kvh) * D, knw, eps, lane, x1, x2);
             const float c1 = bf16_to_f32(c[lane]), c2 = bf16_to_f32(c[lane + half]);
             const float s1 = bf16_to_f32(sv[lane]), s2 = bf16_to_f32(sv[lane + half]);
             const bf16_t k1 = f32_to_bf16(bfr2(x1 * c1) + bfr2(-x2 * s1)), k2 = f32_to_bf16(bfr2(x2 * c2) + bfr2(x1 * s2));
@@ -343,13 +370,15 @@ __global__ __launch_bounds__(ATTN_THREADS) void decode_attn_rope_kernel(const bf
 // Query row s attends to the cache up to slot *pos + s, i.e. also to the keys of rows 0..s of THIS launch: the workgroup rotates and
 // stores those rows of its KV head itself before it reads them (every workgroup of the sequence that needs a row writes the same bits,
 // so nobody waits for anybody), then runs the plain cache attention of decode_attn_bf16_kernel -- bit for bit what rope_bf16_kernel +
-// kv_append_bf16_kernel + decode_attn_bf16_kernel compute in three launches.
-template <int D>
+// kv_append_bf16_kernel + decode_attn_bf16_kernel compute in three launches.  QKN as in decode_attn_rope_kernel: the same head_pair on every
+// q and k row, so a key written here is bitwise the key the decode kernels write, whichever workgroup writes it.
+template <int D, bool QKN>
 __global__ __launch_bounds__(ATTN_THREADS) void suffix_attn_rope_kernel(const bf16_t *__restrict__ qkv, int64_t ld_qkv,
                                                                const bf16_t *__restrict__ cs, const bf16_t *__restrict__ sn, bf16_t *K,
                                                                bf16_t *V, const long long *__restrict__ pos_ptr,
                                                                const unsigned char *__restrict__ mask, bf16_t *__restrict__ out, int nh,
-                                                               int nkv, int S, int maxlen, float scale) {
+                                                               int nkv, int S, int maxlen, float scale, const bf16_t *__restrict__ qnw,
+                                                               const bf16_t *__restrict__ knw, float eps) {
     extern __shared__ __attribute__((aligned(16))) float sm_attn3[];
     float *qs = sm_attn3;                 // [D]  rotated query, f32 of its bf16 value
     float *part = qs + D;                 // ATTN_PART_FLOATS
@@ -365,10 +394,11 @@ __global__ __launch_bounds__(ATTN_THREADS) void suffix_attn_rope_kernel(const bf
     bf16_t *Vb = V + ((int64_t)b * nkv + kvh) * maxlen * D;
     const unsigned char *mrow = mask + (int64_t)r * maxlen;
     if (wave == ATTN_WAVES - 1) {
+        float x1, x2;
+        if (QKN) head_pair<D, true>(qkv + (int64_t)r * ld_qkv + h * D, qnw, eps, lane, x1, x2);
         if (lane < half) {
-            const bf16_t *src = qkv + (int64_t)r * ld_qkv + h * D;
+            if (!QKN) head_pair<D, false>(qkv + (int64_t)r * ld_qkv + h * D, qnw, eps, lane, x1, x2);
             const bf16_t *c = cs + (int64_t)r * D, *sv = sn + (int64_t)r * D;
-            const float x1 = bf16_to_f32(src[lane]), x2 = bf16_to_f32(src[lane + half]);
             const float c1 = bf16_to_f32(c[lane]), c2 = bf16_to_f32(c[lane + half]);
             const float s1 = bf16_to_f32(sv[lane]), s2 = bf16_to_f32(sv[lane + half]);
             qs[lane] = bfr2(bfr2(x1 * c1) + bfr2(-x2 * s1));
@@ -377,11 +407,12 @@ __global__ __launch_bounds__(ATTN_THREADS) void suffix_attn_rope_kernel(const bf
     }
     for (int t = wave; t <= s; t += ATTN_WAVES) {
         const long long p = p0 + t;
-        if (p < 0 || p >= maxlen || lane >= half) continue;
+        if (p < 0 || p >= maxlen || (!QKN && lane >= half)) continue;      // QKN: uniform over the wave, all of its lanes call head_pair
         const int rt = b * S + t;
-        const bf16_t *src = qkv + (int64_t)rt * ld_qkv + (nh + kvh) * D;
+        float x1, x2;
+        head_pair<D, QKN>(qkv + (int64_t)rt * ld_qkv + (nh + kvh) * D, knw, eps, lane, x1, x2);
+        if (QKN && lane >= half) continue;
         const bf16_t *c = cs + (int64_t)rt * D, *sv = sn + (int64_t)rt * D;
-        const float x1 = bf16_to_f32(src[lane]), x2 = bf16_to_f32(src[lane + half]);
         const float c1 = bf16_to_f32(c[lane]), c2 = bf16_to_f32(c[lane + half]);
         const float s1 = bf16_to_f32(sv[lane]), s2 = bf16_to_f32(sv[lane + half]);
         Kb[p * D + lane] = f32_to_bf16(bfr2(x1 * c1) + bfr2(-x2 * s1));
@@ -402,14 +433,16 @@ __global__ __launch_bounds__(ATTN_THREADS) void suffix_attn_rope_kernel(const bf
 // 55 us per layer, most of it G-fold re-reads through L2: profiles/r6_llama64_kernel_stats.csv).  Same access pattern as attn_decode.h --
 // a wave instruction covers RPI whole rows, lane (r, c) holds 16 bytes of row r -- with G query pieces in registers per lane: G dot
 // products per loaded key piece, G axpys per value piece.  Softmax statistics in f32 per head.  The first 256 keys / values are requested
-// before the rotary arithmetic.  Arithmetic per head as decode_attn_rope_kernel up to the f32 summation order of P.V.
-template <int D, int G, int W>      // W waves per workgroup (8 | 16): a wave takes 256 / W keys of a tile
+// before the rotary arithmetic.  Arithmetic per head as decode_attn_rope_kernel up to the f32 summation order of P.V.  QKN as there.
+template <int D, int G, int W, bool QKN>      // W waves per workgroup (8 | 16): a wave takes 256 / W keys of a tile
 __global__ __launch_bounds__(64 * W) void decode_attn_rope_gqa_kernel(const bf16_t *__restrict__ qkv, int64_t ld_qkv,
                                                                    const bf16_t *__restrict__ cs, const bf16_t *__restrict__ sn,
                                                                    int64_t cs0, bf16_t *__restrict__ K, bf16_t *__restrict__ V,
                                                                    const long long *__restrict__ pos_ptr,
                                                                    const unsigned char *__restrict__ mask, int64_t ms0,
-                                                                   bf16_t *__restrict__ out, int nh, int nkv, int maxlen, float scale) {
+                                                                   bf16_t *__restrict__ out, int nh, int nkv, int maxlen, float scale,
+                                                                   const bf16_t *__restrict__ qnw, const bf16_t *__restrict__ knw,
+                                                                   float eps) {
     constexpr int LPR = AttnGeom<D>::LPR, RPI = AttnGeom<D>::RPI, KPW = 256 / W, NI = KPW / RPI, half = D / 2, THREADS = 64 * W;
     auto key_of = [](int j0, int wave, int i, int lane) { return j0 + wave * KPW + i * RPI + lane / LPR; };
     extern __shared__ __attribute__((aligned(16))) float sm_attn3[];
@@ -444,18 +477,20 @@ __global__ __launch_bounds__(64 * W) void decode_attn_rope_gqa_kernel(const bf16
     }
     for (int role = wave; role < G + 2; role += W) {        // roles 0..G-1: query heads; G: the new key; G+1: the new value
         if (role < G) {
+            float x1, x2;
+            if (QKN) head_pair<D, true>(row + (kvh * G + role) * D, qnw, eps, lane, x1, x2);
             if (lane < half) {
-                const bf16_t *src = row + (kvh * G + role) * D;
-                const float x1 = bf16_to_f32(src[lane]), x2 = bf16_to_f32(src[lane + half]);
+                if (!QKN) head_pair<D, false>(row + (kvh * G + role) * D, qnw, eps, lane, x1, x2);
                 const float c1 = bf16_to_f32(c[lane]), c2 = bf16_to_f32(c[lane + half]);
                 const float s1 = bf16_to_f32(sv[lane]), s2 = bf16_to_f32(sv[lane + half]);
                 qs[role * D + lane] = bfr2(bfr2(x1 * c1) + bfr2(-x2 * s1));
                 qs[role * D + lane + half] = bfr2(bfr2(x2 * c2) + bfr2(x1 * s2));
             }
         } else if (role == G) {
+            float x1, x2;
+            if (QKN) head_pair<D, true>(row + (nh + kvh) * D, knw, eps, lane, x1, x2);
             if (lane < half) {
-                const bf16_t *src = row + (nh + kvh) * D;
-                const float x1 = bf16_to_f32(src[lane]), x2 = bf16_to_f32(src[lane + half]);
+                if (!QKN) head_pair<D, false>(row + (nh + kvh) * D, knw, eps, lane, x1, x2);
                 const float c1 = bf16_to_f32(c[lane]), c2 = bf16_to_f32(c[lane + half]);
                 const float s1 = bf16_to_f32(sv[lane]), s2 = bf16_to_f32(sv[lane + half]);
                 const bf16_t k1 = f32_to_bf16(bfr2(x1 * c1) + bfr2(-x2 * s1)), k2 = f32_to_bf16(bfr2(x2 * c2) + bfr2(x1 * s2));
@@ -746,19 +781,15 @@ static int gemv_fused(bool nt, const void *x, int ldx, const void *W, int ldw, c
 
 using namespace ll;
 
-extern "C" {
-
-int ll_gemv_fused_bf16(const void *x, int ldx, const void *W, int ldw, const float *bias, const void *norm_w, float eps,
-                       const void *residual, int ldr, void *out, int ldc, int M, int N, int K, int epi, void *stream) {
-    return gemv_fused(g_gemv_nt != 0, x, ldx, W, ldw, bias, norm_w, eps, residual, ldr, out, ldc, M, N, K, epi, (hipStream_t)stream);
-}
-
-int ll_decode_attn_rope_bf16(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, int64_t cs_stride, void *Kc,
-                             void *Vc, const int64_t *pos, const void *mask, int64_t mask_stride, void *out, int B, int nh,
-                             int nkv, int maxlen, int D, float scale, void *stream) {
-    LL_CHECK(qkv && cos && sin && Kc && Vc && pos && mask && out, "ll_decode_attn_rope_bf16: null argument");
+template <bool QKN>
+static int decode_attn_rope(const char *who, const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, int64_t cs_stride, void *Kc,
+                            void *Vc, const int64_t *pos, const void *mask, int64_t mask_stride, void *out, int B, int nh, int nkv,
+                            int maxlen, int D, float scale, const void *q_norm_w, const void *k_norm_w, float eps, void *stream) {
+    LL_CHECK(qkv && cos && sin && Kc && Vc && pos && mask && out, "%s: null argument", who);
+    LL_CHECK(!QKN || (q_norm_w && k_norm_w), "%s: null norm weight", who);
+    LL_CHECK(!QKN || eps > 0.f, "%s: eps must be positive", who);
     LL_CHECK((D == 64 || D == 128) && B >= 1 && nkv >= 1 && nh % nkv == 0 && maxlen >= 1 && maxlen <= 16384 && ld_qkv % 8 == 0,
-             "ll_decode_attn_rope_bf16: unsupported shape");
+             "%s: unsupported shape", who);
     // many sequences: one workgroup per (KV head, sequence) for the group sizes of the supported models (Llama-3.1-8B / Mistral-7B 4,
     // Qwen2-7B 7, the toy models 2); up to 16 sequences keep the per-head kernel (bit-identical to the op-by-op path)
     const int G = nh / nkv;
@@ -771,12 +802,13 @@ int ll_decode_attn_rope_bf16(const void *qkv, int64_t ld_qkv, const void *cos, c
     do {                                                                                                                                 \
         static size_t attr = 0;                                                                                                          \
         if (l3 > attr) {                                                                                                                 \
-            LL_HIP(hipFuncSetAttribute((const void *)decode_attn_rope_gqa_kernel<D_, G_, W_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3)); \
+            LL_HIP(hipFuncSetAttribute((const void *)decode_attn_rope_gqa_kernel<D_, G_, W_, QKN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3)); \
             attr = l3;                                                                                                                   \
         }                                                                                                                                \
-        hipLaunchKernelGGL((decode_attn_rope_gqa_kernel<D_, G_, W_>), g3, dim3(64 * W_), l3, (hipStream_t)stream, (const bf16_t *)qkv, ld_qkv, \
+        hipLaunchKernelGGL((decode_attn_rope_gqa_kernel<D_, G_, W_, QKN>), g3, dim3(64 * W_), l3, (hipStream_t)stream, (const bf16_t *)qkv, ld_qkv, \
                            (const bf16_t *)cos, (const bf16_t *)sin, cs_stride, (bf16_t *)Kc, (bf16_t *)Vc, (const long long *)pos,      \
-                           (const unsigned char *)mask, mask_stride, (bf16_t *)out, nh, nkv, maxlen, scale);                            \
+                           (const unsigned char *)mask, mask_stride, (bf16_t *)out, nh, nkv, maxlen, scale,                             \
+                           (const bf16_t *)q_norm_w, (const bf16_t *)k_norm_w, eps);                                                    \
     } while (0)
             // sixteen waves for groups of up to four heads (16 keys per wave and tile: <= 128 VGPRs), eight for seven (Qwen2-7B)
             if (D == 128) {
@@ -795,17 +827,70 @@ int ll_decode_attn_rope_bf16(const void *qkv, int64_t ld_qkv, const void *cos, c
     do {                                                                                                                                 \
         static size_t attr = 64 * 1024;       /* > 64 KB of dynamic LDS (maxlen > ~12 k keys) needs the attribute */                    \
         if (lds > attr) {                                                                                                                \
-            LL_HIP(hipFuncSetAttribute((const void *)decode_attn_rope_kernel<D_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            LL_HIP(hipFuncSetAttribute((const void *)decode_attn_rope_kernel<D_, QKN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
             attr = lds;                                                                                                                  \
         }                                                                                                                                \
-        hipLaunchKernelGGL((decode_attn_rope_kernel<D_>), grid, dim3(ATTN_THREADS), lds, (hipStream_t)stream, (const bf16_t *)qkv,       \
+        hipLaunchKernelGGL((decode_attn_rope_kernel<D_, QKN>), grid, dim3(ATTN_THREADS), lds, (hipStream_t)stream, (const bf16_t *)qkv,       \
                            ld_qkv, (const bf16_t *)cos, (const bf16_t *)sin, cs_stride, (bf16_t *)Kc, (bf16_t *)Vc,                      \
-                           (const long long *)pos, (const unsigned char *)mask, mask_stride, (bf16_t *)out, nh, nkv, maxlen, scale);    \
+                           (const long long *)pos, (const unsigned char *)mask, mask_stride, (bf16_t *)out, nh, nkv, maxlen, scale,     \
+                           (const bf16_t *)q_norm_w, (const bf16_t *)k_norm_w, eps);                                                    \
     } while (0)
     if (D == 128) LL_ATTN(128); else LL_ATTN(64);
 #undef LL_ATTN
     LL_LAUNCH_CHECK();
     return LL_OK;
+}
+
+template <bool QKN>
+static int suffix_attn_rope(const char *who, const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, void *Kc, void *Vc,
+                            const int64_t *pos, const void *mask, void *out, int B, int S, int nh, int nkv, int maxlen, int D, float scale,
+                            const void *q_norm_w, const void *k_norm_w, float eps, void *stream) {
+    LL_CHECK(qkv && cos && sin && Kc && Vc && pos && mask && out, "%s: null argument", who);
+    LL_CHECK(!QKN || (q_norm_w && k_norm_w), "%s: null norm weight", who);
+    LL_CHECK(!QKN || eps > 0.f, "%s: eps must be positive", who);
+    LL_CHECK((D == 64 || D == 128) && B >= 1 && S >= 1 && S <= 16 && nkv >= 1 && nh % nkv == 0 && maxlen >= 1 && maxlen <= 16384 &&
+                 ld_qkv % 8 == 0,
+             "%s: unsupported shape", who);
+    const size_t lds = ((size_t)maxlen + D + ATTN_PART_FLOATS) * 4;
+    dim3 grid(nh, B * S);
+#define LL_ATTN(D_)                                                                                                                      \
+    do {                                                                                                                                 \
+        static size_t attr = 64 * 1024;       /* > 64 KB of dynamic LDS (maxlen > ~12 k keys) needs the attribute */                    \
+        if (lds > attr) {                                                                                                                \
+            LL_HIP(hipFuncSetAttribute((const void *)suffix_attn_rope_kernel<D_, QKN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            attr = lds;                                                                                                                  \
+        }                                                                                                                                \
+        hipLaunchKernelGGL((suffix_attn_rope_kernel<D_, QKN>), grid, dim3(ATTN_THREADS), lds, (hipStream_t)stream, (const bf16_t *)qkv,       \
+                           ld_qkv, (const bf16_t *)cos, (const bf16_t *)sin, (bf16_t *)Kc, (bf16_t *)Vc, (const long long *)pos,         \
+                           (const unsigned char *)mask, (bf16_t *)out, nh, nkv, S, maxlen, scale, (const bf16_t *)q_norm_w,             \
+                           (const bf16_t *)k_norm_w, eps);                                                                              \
+    } while (0)
+    if (D == 128) LL_ATTN(128); else LL_ATTN(64);
+#undef LL_ATTN
+    LL_LAUNCH_CHECK();
+    return LL_OK;
+}
+
+extern "C" {
+
+int ll_gemv_fused_bf16(const void *x, int ldx, const void *W, int ldw, const float *bias, const void *norm_w, float eps,
+                       const void *residual, int ldr, void *out, int ldc, int M, int N, int K, int epi, void *stream) {
+    return gemv_fused(g_gemv_nt != 0, x, ldx, W, ldw, bias, norm_w, eps, residual, ldr, out, ldc, M, N, K, epi, (hipStream_t)stream);
+}
+
+int ll_decode_attn_rope_bf16(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, int64_t cs_stride, void *Kc,
+                             void *Vc, const int64_t *pos, const void *mask, int64_t mask_stride, void *out, int B, int nh,
+                             int nkv, int maxlen, int D, float scale, void *stream) {
+    return decode_attn_rope<false>("ll_decode_attn_rope_bf16", qkv, ld_qkv, cos, sin, cs_stride, Kc, Vc, pos, mask, mask_stride, out, B, nh,
+                                   nkv, maxlen, D, scale, nullptr, nullptr, 0.f, stream);
+}
+
+int ll_decode_attn_rope_qkn_bf16(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, int64_t cs_stride, void *Kc,
+                                 void *Vc, const int64_t *pos, const void *mask, int64_t mask_stride, void *out, int B, int nh,
+                                 int nkv, int maxlen, int D, float scale, const void *q_norm_w, const void *k_norm_w, float eps,
+                                 void *stream) {
+    return decode_attn_rope<true>("ll_decode_attn_rope_qkn_bf16", qkv, ld_qkv, cos, sin, cs_stride, Kc, Vc, pos, mask, mask_stride, out, B,
+                                  nh, nkv, maxlen, D, scale, q_norm_w, k_norm_w, eps, stream);
 }
 
 int ll_decode_prologue(const int64_t *position_ids, const float *inv_freq, float attention_scaling, const int64_t *mask2d,
@@ -863,27 +948,15 @@ int ll_suffix_prologue_dyn(const int64_t *position_ids, const float *inv_freq0, 
 
 int ll_suffix_attn_rope_bf16(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, void *Kc, void *Vc, const int64_t *pos,
                              const void *mask, void *out, int B, int S, int nh, int nkv, int maxlen, int D, float scale, void *stream) {
-    LL_CHECK(qkv && cos && sin && Kc && Vc && pos && mask && out, "ll_suffix_attn_rope_bf16: null argument");
-    LL_CHECK((D == 64 || D == 128) && B >= 1 && S >= 1 && S <= 16 && nkv >= 1 && nh % nkv == 0 && maxlen >= 1 && maxlen <= 16384 &&
-                 ld_qkv % 8 == 0,
-             "ll_suffix_attn_rope_bf16: unsupported shape");
-    const size_t lds = ((size_t)maxlen + D + ATTN_PART_FLOATS) * 4;
-    dim3 grid(nh, B * S);
-#define LL_ATTN(D_)                                                                                                                      \
-    do {                                                                                                                                 \
-        static size_t attr = 64 * 1024;       /* > 64 KB of dynamic LDS (maxlen > ~12 k keys) needs the attribute */                    \
-        if (lds > attr) {                                                                                                                \
-            LL_HIP(hipFuncSetAttribute((const void *)suffix_attn_rope_kernel<D_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            attr = lds;                                                                                                                  \
-        }                                                                                                                                \
-        hipLaunchKernelGGL((suffix_attn_rope_kernel<D_>), grid, dim3(ATTN_THREADS), lds, (hipStream_t)stream, (const bf16_t *)qkv,       \
-                           ld_qkv, (const bf16_t *)cos, (const bf16_t *)sin, (bf16_t *)Kc, (bf16_t *)Vc, (const long long *)pos,         \
-                           (const unsigned char *)mask, (bf16_t *)out, nh, nkv, S, maxlen, scale);                                      \
-    } while (0)
-    if (D == 128) LL_ATTN(128); else LL_ATTN(64);
-#undef LL_ATTN
-    LL_LAUNCH_CHECK();
-    return LL_OK;
+    return suffix_attn_rope<false>("ll_suffix_attn_rope_bf16", qkv, ld_qkv, cos, sin, Kc, Vc, pos, mask, out, B, S, nh, nkv, maxlen, D,
+                                   scale, nullptr, nullptr, 0.f, stream);
+}
+
+int ll_suffix_attn_rope_qkn_bf16(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, void *Kc, void *Vc, const int64_t *pos,
+                                 const void *mask, void *out, int B, int S, int nh, int nkv, int maxlen, int D, float scale,
+                                 const void *q_norm_w, const void *k_norm_w, float eps, void *stream) {
+    return suffix_attn_rope<true>("ll_suffix_attn_rope_qkn_bf16", qkv, ld_qkv, cos, sin, Kc, Vc, pos, mask, out, B, S, nh, nkv, maxlen, D,
+                                  scale, q_norm_w, k_norm_w, eps, stream);
 }
 
 // Times ll_gemv_fused_bf16 on synthetic operands, cycling through `nweights` distinct weight matrices (defeats the

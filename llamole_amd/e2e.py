@@ -34,6 +34,14 @@ LLM_CONFIGS = {
     "tiny": dict(cls="Qwen2", hidden_size=256, num_hidden_layers=2, num_attention_heads=4, num_key_value_heads=2,
                  intermediate_size=512, vocab_size=2048, max_position_embeddings=2048, rope_theta=10000.0,
                  rms_norm_eps=1e-6, tie_word_embeddings=False),
+    # Qwen3 layout: per-head q / k RMSNorm, no q/k/v bias, head_dim independent of hidden / heads (published Qwen3-8B widths; the toy model keeps
+    # nq = heads * head_dim = 512 != hidden like the real ones)
+    "qwen3-8b": dict(cls="Qwen3", hidden_size=4096, num_hidden_layers=36, num_attention_heads=32, num_key_value_heads=8, head_dim=128,
+                     intermediate_size=12288, vocab_size=151936, max_position_embeddings=40960, rope_theta=1000000.0,
+                     rms_norm_eps=1e-6, tie_word_embeddings=False),
+    "tiny-qwen3": dict(cls="Qwen3", hidden_size=256, num_hidden_layers=2, num_attention_heads=4, num_key_value_heads=2, head_dim=128,
+                       intermediate_size=512, vocab_size=2048, max_position_embeddings=2048, rope_theta=10000.0,
+                       rms_norm_eps=1e-6, tie_word_embeddings=False),
 }
 
 # rope_parameters of the published meta-llama/Meta-Llama-3.1-8B-Instruct config.json (rope_scaling there): the "llama-3.1-8b" entry above has the
@@ -108,6 +116,22 @@ def build_llm(name: str, device, dtype=torch.bfloat16, seed: int = 0, **override
     for p in model.parameters():
         p.requires_grad = False
     return model
+
+
+def randomize_head_norms(model, seed: int = 1) -> int:
+    """Draw the per-head q_norm / k_norm weights of a Qwen3-layout model as bf16(1 + 0.5 N(0, 1)), q and k from different draws.  HF
+    initialises them to ones, which hides a missing or swapped weight; ``build_llm`` stays as it is, tests and timing tools call this."""
+    g = torch.Generator().manual_seed(seed)
+    n = 0
+    base = getattr(model, "model", model)
+    with torch.no_grad():
+        for layer in base.layers:
+            for name in ("q_norm", "k_norm"):
+                m = getattr(layer.self_attn, name, None)
+                if m is not None:
+                    m.weight.copy_((1 + 0.5 * torch.randn(m.weight.shape, generator=g)).to(m.weight.dtype))
+                    n += 1
+    return n
 
 
 def build_orchestrator(llm, graph_decoder, device, dtype=torch.bfloat16):

@@ -627,6 +627,10 @@ class _FusedLayer:
         self.nh, self.nkv = self.nq // self.D, self.nkv_dim // self.D
         self.H = q.in_features
         self.scaling = float(att.scaling)
+        # Qwen3 layout: an RMSNorm over head_dim on every q and k head row in front of the rotation, done inside the attention launch; the
+        # modules stay the owners of the weights (read at every call: no copy to keep in step)
+        self.qn, self.kn = getattr(att, "q_norm", None), getattr(att, "k_norm", None)
+        self.qk_eps = float(self.qn.variance_epsilon) if self.qn is not None else 0.0
         self.wo = o.weight.detach()
         self.bo = o.bias.detach().float().contiguous() if o.bias is not None else None
         self.bo_key = _versions(o.bias)
@@ -726,12 +730,18 @@ class _FusedLayer:
         pos = cache.layers[0].cumulative_length
         cos, sin = pe
         att = torch.empty(B, self.nq, dtype=torch.bfloat16, device=device)
-        rc = self.lib.ll_decode_attn_rope_bf16(qkv.data_ptr(), nqkv, cos.data_ptr(), sin.data_ptr(),
-                                               0 if cos.shape[0] == 1 else cos.stride(0), cl.keys.data_ptr(), cl.values.data_ptr(),
-                                               pos.data_ptr(), mask.data_ptr(), mask.stride(0), att.data_ptr(), B, self.nh, self.nkv,
-                                               cl.keys.shape[2], self.D, self.scaling, torch.cuda.current_stream().cuda_stream)
+        args = (qkv.data_ptr(), nqkv, cos.data_ptr(), sin.data_ptr(), 0 if cos.shape[0] == 1 else cos.stride(0), cl.keys.data_ptr(),
+                cl.values.data_ptr(), pos.data_ptr(), mask.data_ptr(), mask.stride(0), att.data_ptr(), B, self.nh, self.nkv,
+                cl.keys.shape[2], self.D, self.scaling)
+        if self.qn is not None:
+            name = "ll_decode_attn_rope_qkn_bf16"
+            rc = self.lib.ll_decode_attn_rope_qkn_bf16(*args, self.qn.weight.data_ptr(), self.kn.weight.data_ptr(), self.qk_eps,
+                                                       torch.cuda.current_stream().cuda_stream)
+        else:
+            name = "ll_decode_attn_rope_bf16"
+            rc = self.lib.ll_decode_attn_rope_bf16(*args, torch.cuda.current_stream().cuda_stream)
         if rc != 0:
-            _lib.check(rc, "ll_decode_attn_rope_bf16")
+            _lib.check(rc, name)
         return att
 
     def run64(self, h, mask, cache, pe, pre=None, next_norm=None):
@@ -760,19 +770,10 @@ class _FusedLayer:
         if B > MAX_ROWS16:
             return self.run64(h, mask, cache, pe)[0]
         x = h.view(B, H)
-        cl = cache.layers[self.layer_idx]
-        pos = cache.layers[0].cumulative_length
-        cos, sin = pe
         nqkv = self.nq + 2 * self.nkv_dim
         pq = self.pq or (None, None, None, None)
         qkv = self._gemv(x, self.wqkv, self.bqkv, self.n1.weight, self.eps1, None, nqkv, H, 0, pq[0], "qkv")
-        att = torch.empty(B, self.nq, dtype=torch.bfloat16, device=h.device)
-        rc = self.lib.ll_decode_attn_rope_bf16(qkv.data_ptr(), nqkv, cos.data_ptr(), sin.data_ptr(),
-                                               0 if cos.shape[0] == 1 else cos.stride(0), cl.keys.data_ptr(), cl.values.data_ptr(),
-                                               pos.data_ptr(), mask.data_ptr(), mask.stride(0), att.data_ptr(), B, self.nh, self.nkv,
-                                               cl.keys.shape[2], self.D, self.scaling, torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            _lib.check(rc, "ll_decode_attn_rope_bf16")
+        att = self._attn(qkv, nqkv, mask, cache, pe, B, h.device)
         h1 = self._gemv(att, self.wo, self.bo, None, 0.0, x, H, self.nq, 1, pq[1], "o")
         act = self._gemv(h1, self.wgu, None, self.n2.weight, self.eps2, None, self.I, H, 2, pq[2], "gate_up")
         h2 = self._gemv(act, self.wdown, None, None, 0.0, h1, H, self.I, 1, pq[3], "down")
@@ -791,11 +792,17 @@ class _FusedLayer:
         pq = self.pq or (None, None, None, None)
         qkv = self._gemv(x, self.wqkv, self.bqkv, self.n1.weight, self.eps1, None, nqkv, H, 0, pq[0], "qkv")
         att = torch.empty(R, self.nq, dtype=torch.bfloat16, device=h.device)
-        rc = self.lib.ll_suffix_attn_rope_bf16(qkv.data_ptr(), nqkv, cos.data_ptr(), sin.data_ptr(), cl.keys.data_ptr(), cl.values.data_ptr(),
-                                               pos.data_ptr(), mask.data_ptr(), att.data_ptr(), B, S, self.nh, self.nkv, cl.keys.shape[2],
-                                               self.D, self.scaling, torch.cuda.current_stream().cuda_stream)
+        args = (qkv.data_ptr(), nqkv, cos.data_ptr(), sin.data_ptr(), cl.keys.data_ptr(), cl.values.data_ptr(), pos.data_ptr(), mask.data_ptr(),
+                att.data_ptr(), B, S, self.nh, self.nkv, cl.keys.shape[2], self.D, self.scaling)
+        if self.qn is not None:
+            name = "ll_suffix_attn_rope_qkn_bf16"
+            rc = self.lib.ll_suffix_attn_rope_qkn_bf16(*args, self.qn.weight.data_ptr(), self.kn.weight.data_ptr(), self.qk_eps,
+                                                       torch.cuda.current_stream().cuda_stream)
+        else:
+            name = "ll_suffix_attn_rope_bf16"
+            rc = self.lib.ll_suffix_attn_rope_bf16(*args, torch.cuda.current_stream().cuda_stream)
         if rc != 0:
-            _lib.check(rc, "ll_suffix_attn_rope_bf16")
+            _lib.check(rc, name)
         h1 = self._gemv(att, self.wo, self.bo, None, 0.0, x, H, self.nq, 1, pq[1], "o")
         act = self._gemv(h1, self.wgu, None, self.n2.weight, self.eps2, None, self.I, H, 2, pq[2], "gate_up")
         h2 = self._gemv(act, self.wdown, None, None, 0.0, h1, H, self.I, 1, pq[3], "down")
@@ -812,8 +819,61 @@ def _layer_forward(self, hidden_states, attention_mask=None, position_ids=None, 
                                **kwargs)
 
 
+def _head_norm_declined(att) -> Optional[str]:
+    """The structural part of ``decoder_layer_declined`` for per-head q / k norms (Qwen3 layout): both or none, the model's own *RMSNorm with
+    ``variance_epsilon`` (the condition of ``accelerate_elementwise``), one weight per element of a head, one eps."""
+    qn, kn = getattr(att, "q_norm", None), getattr(att, "k_norm", None)
+    if qn is None and kn is None:
+        return None
+    if qn is None or kn is None:
+        return "only one of q_norm / k_norm"
+    for name, m in (("q_norm", qn), ("k_norm", kn)):
+        if not (type(m).__name__.endswith("RMSNorm") and hasattr(m, "variance_epsilon") and isinstance(getattr(m, "weight", None), torch.Tensor)):
+            return f"{name} is not an RMSNorm with variance_epsilon"
+        if m.weight.numel() != getattr(att, "head_dim", 0):
+            return f"{name} is not a norm over head_dim"
+    if float(qn.variance_epsilon) != float(kn.variance_epsilon):
+        return "q_norm and k_norm differ in variance_epsilon"
+    return None
+
+
+def decoder_layer_declined(layer: nn.Module) -> Optional[str]:
+    """Why ``fuse_decoder_layers`` would not fuse this decoder layer (None: it would) -- the sibling of ``model_decode_declined``.  Structural
+    reasons come first and dtype / device reasons last, so the layout of a model can be judged on the CPU."""
+    att, mlp = getattr(layer, "self_attn", None), getattr(layer, "mlp", None)
+    if att is None or mlp is None:
+        return "no self_attn / mlp"
+    if hasattr(layer, "_ll_fused"):
+        return "already installed"
+    if not (all(type(getattr(att, a, None)) is nn.Linear for a in ("q_proj", "k_proj", "v_proj", "o_proj"))
+            and all(type(getattr(mlp, a, None)) is nn.Linear for a in ("gate_proj", "up_proj", "down_proj"))):
+        return "projections are not plain nn.Linear"
+    if not _is_silu(getattr(mlp, "act_fn", None)):
+        return "activation is not SiLU"
+    if not (hasattr(layer, "input_layernorm") and hasattr(layer, "post_attention_layernorm")
+            and hasattr(layer.input_layernorm, "variance_epsilon")):
+        return "no RMSNorm pair with variance_epsilon"
+    if getattr(att, "head_dim", 0) not in (64, 128):
+        return "head_dim is not 64 or 128"
+    if att.q_proj.in_features % 8 != 0 or att.q_proj.in_features > 8192:
+        return "hidden size is not a multiple of 8 up to 8192"
+    if mlp.gate_proj.bias is not None or mlp.up_proj.bias is not None or mlp.down_proj.bias is not None:
+        return "MLP bias"
+    if getattr(att, "sliding_window", None) is not None:
+        return "sliding-window layer"
+    why = _head_norm_declined(att)
+    if why is not None:
+        return why
+    norms = [m for m in (getattr(att, "q_norm", None), getattr(att, "k_norm", None)) if m is not None]
+    if att.q_proj.weight.dtype != torch.bfloat16 or any(m.weight.dtype != torch.bfloat16 for m in norms):
+        return "weights are not bf16"
+    if not att.q_proj.weight.is_cuda or not all(m.weight.is_cuda for m in norms):
+        return "weights are not on the device"
+    return None
+
+
 def fuse_decoder_layers(model: nn.Module) -> int:
-    """Run every decoder layer of a Qwen2 / Llama / Mistral-layout HF model as five launches at decode (batch <= 16), static cache with the fused append of ``fuse_cache_update``, boolean sdpa-style mask.  Any other call --
+    """Run every decoder layer of a Qwen2 / Llama / Mistral / Qwen3-layout HF model as five launches at decode (batch <= 16), static cache with the fused append of ``fuse_cache_update``, boolean sdpa-style mask.  Any other call --
     prefill, larger batches, a dynamic cache -- takes the layer's previous forward.  Returns the number of patched layers."""
     lib = _lib.load()
     base = getattr(model, "model", model)
@@ -822,19 +882,7 @@ def fuse_decoder_layers(model: nn.Module) -> int:
         return 0
     n = 0
     for layer in layers:
-        att, mlp = getattr(layer, "self_attn", None), getattr(layer, "mlp", None)
-        if att is None or mlp is None or hasattr(layer, "_ll_fused"):
-            continue
-        ok = (all(type(getattr(att, a, None)) is nn.Linear for a in ("q_proj", "k_proj", "v_proj", "o_proj"))
-              and all(type(getattr(mlp, a, None)) is nn.Linear for a in ("gate_proj", "up_proj", "down_proj"))
-              and _is_silu(getattr(mlp, "act_fn", None)) and hasattr(layer, "input_layernorm")
-              and hasattr(layer, "post_attention_layernorm") and hasattr(layer.input_layernorm, "variance_epsilon")
-              and att.q_proj.weight.dtype == torch.bfloat16 and att.q_proj.weight.is_cuda
-              and getattr(att, "head_dim", 0) in (64, 128) and att.q_proj.in_features % 8 == 0
-              and att.q_proj.in_features <= 8192 and mlp.gate_proj.bias is None and mlp.up_proj.bias is None
-              and mlp.down_proj.bias is None and getattr(att, "sliding_window", None) is None
-              and not hasattr(att, "q_norm"))
-        if not ok:
+        if decoder_layer_declined(layer) is not None:
             continue
         layer._ll_fused = _FusedLayer(lib, layer)
         layer._ll_layer_orig = layer.forward
@@ -1083,7 +1131,11 @@ def accelerate_llm(model: nn.Module, linears: bool = True, fuse: bool = True, la
         info.update(accelerate_elementwise(model))
         info["decode_attention"] = bool(use_decode_attention(model))
         if info["decode_attention"] and layers:
+            all_layers = list(getattr(getattr(model, "model", model), "layers", None) or [])
+            reasons = [decoder_layer_declined(l) for l in all_layers]
             info["decoder_layers_5_launches"] = fuse_decoder_layers(model)
+            if info["decoder_layers_5_launches"] < len(all_layers):
+                info["decoder_layers_declined"] = next((r for r in reasons if r is not None), None)
             if model_decode:
                 declined = model_decode_declined(model)
                 info["decode_prologue_1_launch"] = fuse_model_decode(model)
