@@ -445,6 +445,48 @@ int ll_gemv_fused_wq(const void *x, int ldx, const void *packed, int bits, const
 int ll_linear_rows16_wq(const void *x, int ldx, const void *packed, int bits, const float *bias, const void *norm_w, float eps,
                         const void *residual, int ldr, void *out, int ldc, int M, int N, int K, int epi, void *stream);
 
+/* ---- sparse mixture-of-experts MLP block at decode (Qwen3-MoE layout; llamole_amd/csrc/llm_moe.hip) --------------------------------
+ * Replaces Qwen3MoeSparseMoeBlock.forward (transformers modeling_qwen3_moe.py: Qwen3MoeTopKRouter + Qwen3MoeExperts) + the decoder layer's
+ * residual add for 1..64 token rows.  The router logits are NOT an entry point of their own: they are ll_gemv_fused_bf16 /
+ * ll_linear_rows16_bf16 with W = mlp.gate.weight [E, H], the post-attention RMSNorm as prologue and the LL_GEMV_PLAIN epilogue (HF's
+ * F.linear on the normalised row, rounded to bf16).  All three calls are enqueued on `stream`, read the routing on the device only (no
+ * host synchronisation) and have a launch geometry that depends on (M, E, top_k, H, I) alone, so a captured graph replays them.
+ * Bounds of all three: 1 <= M <= 64, E <= 256, 1 <= top_k <= min(E, 8); beyond them LL_EINVAL (ll_moe_workspace_bytes: -1), nothing is launched.
+ *
+ * ll_moe_workspace_bytes : bytes of the device workspace (16-byte aligned) the two calls below share for these sizes; its layout is private.
+ *     A workspace sized for 64 rows serves every smaller M.
+ *
+ * ll_moe_route_bf16 : logits [M, E] bf16 (row stride ld elements) -> idx [M, top_k] int32 and w [M, top_k] bf16, both contiguous, in slot
+ *     order (Qwen3MoeTopKRouter.forward):
+ *       selection      the top_k largest logits in descending order, equal logits by the lower expert index (softmax is monotone: this is
+ *                      torch.topk(softmax(logits)) wherever torch's result is determined); a NaN logit ranks below every number;
+ *       probabilities  p_j = exp(l_j - max) / sum_all_i exp(l_i - max), f32;
+ *       weights        w_j = p_j / sum_selected p (f32, summed in slot order) when norm_topk != 0, else p_j; ONE rounding to bf16.
+ *     It also writes the grouping of the (row, slot) pairs by expert that ll_moe_experts_bf16 reads into the workspace.
+ *
+ * ll_moe_experts_bf16 : x [M, H] = the UN-normalised residual stream (row stride ldx), norm_w [H] / eps = the post-attention RMSNorm,
+ *     idx / w / workspace = what ll_moe_route_bf16 wrote for the same (M, E, top_k) (expert ids are trusted to lie in [0, E); addresses are
+ *     clamped into the operands whatever the workspace holds), Wgu [E, 2I, H] (gate rows then up rows per expert:
+ *     Qwen3MoeExperts.gate_up_proj in place), Wd [E, H, I] (down_proj in place), residual [M, H] (stride ldr), out [M, H] (stride ldo;
+ *     may alias residual).  For token row m and slot j with e = idx[m, j]:
+ *         a_mj  = the LL_GEMV_SILU_MUL result of ll_gemv_fused_bf16 with its RMSNorm prologue on x_m and W = Wgu[e]
+ *                 (the same device function: same arithmetic, same bf16 roundings)
+ *         y_mj  = bf16( a_mj . Wd[e]^T )                          f32 accumulation, the dense GEMV's order
+ *         z_mj  = bf16( float(w_mj) * float(y_mj) )
+ *         out_m = bf16( float(residual_m) + float( bf16( sum_j z_mj ) ) )      sum in f32, slot order, ONE rounding
+ *     This is HF's default experts path (grouped_mm: view(tokens, k, H).sum(dim=1)) followed by the layer's residual add.  The one
+ *     deviation: HF's `eager` experts implementation accumulates the k terms in bf16 with index_add_ in expert order instead.
+ *     A token row that is the only one of its expert gets bit for bit what ll_gemv_fused_bf16 gives on that expert's matrices.
+ *     Three launches (gate|up, down, slot sum + residual) over min(E, M * top_k) active-expert slots: experts nobody chose cost nothing,
+ *     and an expert's matrices are streamed from HBM once per launch however many rows chose it (passes of up to 4 rows).
+ *     Sizes: H % 8 == 0, 8 <= H <= 8192, I % 8 == 0, 8 <= I <= 32768, strides multiples of 8, operands 16-byte aligned, eps > 0. */
+int64_t ll_moe_workspace_bytes(int M, int E, int top_k, int H, int I);
+int ll_moe_route_bf16(const void *logits, int ld, int M, int E, int top_k, int norm_topk, int32_t *idx, void *w, void *workspace,
+                      int64_t workspace_bytes, void *stream);
+int ll_moe_experts_bf16(const void *x, int ldx, const void *norm_w, float eps, const int32_t *idx, const void *w, const void *Wgu,
+                        const void *Wd, const void *residual, int ldr, void *out, int ldo, int M, int E, int top_k, int H, int I,
+                        void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,16 @@ LLM_CONFIGS = {
     "tiny-qwen3": dict(cls="Qwen3", hidden_size=256, num_hidden_layers=2, num_attention_heads=4, num_key_value_heads=2, head_dim=128,
                        intermediate_size=512, vocab_size=2048, max_position_embeddings=2048, rope_theta=10000.0,
                        rms_norm_eps=1e-6, tie_word_embeddings=False),
+    # Qwen3-MoE layout: the Qwen3 attention with a sparse mixture-of-experts MLP (softmax router over all experts, top-k, renormalised; published
+    # Qwen3-30B-A3B widths).  A mixed model is build_llm("tiny-qwen3-moe", ..., mlp_only_layers=[0]): layer 0 dense, layer 1 sparse
+    "qwen3-30b-a3b": dict(cls="Qwen3Moe", hidden_size=2048, num_hidden_layers=48, num_attention_heads=32, num_key_value_heads=4, head_dim=128,
+                          num_experts=128, num_experts_per_tok=8, moe_intermediate_size=768, intermediate_size=6144, vocab_size=151936,
+                          max_position_embeddings=40960, rope_theta=1000000.0, rms_norm_eps=1e-6, norm_topk_prob=True,
+                          decoder_sparse_step=1, mlp_only_layers=[], tie_word_embeddings=False),
+    "tiny-qwen3-moe": dict(cls="Qwen3Moe", hidden_size=256, num_hidden_layers=2, num_attention_heads=4, num_key_value_heads=2, head_dim=128,
+                           num_experts=8, num_experts_per_tok=2, moe_intermediate_size=128, intermediate_size=512, vocab_size=2048,
+                           max_position_embeddings=2048, rope_theta=10000.0, rms_norm_eps=1e-6, norm_topk_prob=True,
+                           decoder_sparse_step=1, mlp_only_layers=[], tie_word_embeddings=False),
 }
 
 # rope_parameters of the published meta-llama/Meta-Llama-3.1-8B-Instruct config.json (rope_scaling there): the "llama-3.1-8b" entry above has the

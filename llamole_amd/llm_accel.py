@@ -616,7 +616,7 @@ class _FusedLayer:
     epilogues."""
 
     def __init__(self, lib, layer):
-        att, mlp = layer.self_attn, layer.mlp
+        att = layer.self_attn
         self.lib = lib
         self.layer_idx = att.layer_idx
         q, k, v, o = att.q_proj, att.k_proj, att.v_proj, att.o_proj
@@ -634,6 +634,22 @@ class _FusedLayer:
         self.wo = o.weight.detach()
         self.bo = o.bias.detach().float().contiguous() if o.bias is not None else None
         self.bo_key = _versions(o.bias)
+        self.n1, self.n2 = layer.input_layernorm, layer.post_attention_layernorm
+        self.eps1, self.eps2 = float(self.n1.variance_epsilon), float(self.n2.variance_epsilon)
+        self._init_mlp(layer, (q, k, v, o))
+        self.p64 = None         # packed copies of the matrices for 17..64 rows (made at the first such step)
+        # quantization_bit: the MX codes of [q|k|v], o_proj, [gate|up], down_proj (made from the rounded bf16 matrices, which stay: they serve the
+        # prefill and 17..64 rows); None = the layer runs on bf16 weights (not quantised, or a K that is not a multiple of 32)
+        bits = {m.__dict__.get("_ll_wq_bits") for m in self._mods}
+        self.wq_bits = bits.pop() if len(bits) == 1 else None
+        self.pq = None
+        self.use_wq = True      # off: the bf16 kernels on the dequantised weights (tests, A/B timing)
+        if self.wq_bits is not None and self.stream_ok and self.wq_ok:
+            self.pq = tuple(_PackedWQ(lib, w, self.wq_bits, key) for w, key in zip(self._srcs(), self._keys64()))
+
+    def _init_mlp(self, layer, attn_mods):
+        """The dense gated MLP: the concatenated gate|up copy and down_proj."""
+        mlp = layer.mlp
         wgu = getattr(mlp, "_ll_gate_up", None)
         if wgu is None:
             wgu = torch.cat([mlp.gate_proj.weight.detach(), mlp.up_proj.weight.detach()], dim=0).contiguous()
@@ -641,22 +657,16 @@ class _FusedLayer:
         self.wgu = wgu
         self.I = mlp.gate_proj.out_features
         self.wdown = mlp.down_proj.weight.detach()
-        self.n1, self.n2 = layer.input_layernorm, layer.post_attention_layernorm
-        self.eps1, self.eps2 = float(self.n1.variance_epsilon), float(self.n2.variance_epsilon)
         self.stream_ok = self.H % 32 == 0 and self.nq % 32 == 0 and self.I % 32 == 0 and self.n1.weight.dtype == torch.bfloat16
-        self._mods = (q, k, v, o, mlp.gate_proj, mlp.up_proj, mlp.down_proj)
-        self.p64 = None         # packed copies of the four matrices for 17..64 rows (made at the first such step)
-        # quantization_bit: the MX codes of [q|k|v], o_proj, [gate|up], down_proj (made from the rounded bf16 matrices, which stay: they serve the
-        # prefill and 17..64 rows); None = the layer runs on bf16 weights (not quantised, or a K that is not a multiple of 32)
-        bits = {m.__dict__.get("_ll_wq_bits") for m in self._mods}
-        self.wq_bits = bits.pop() if len(bits) == 1 else None
-        self.pq = None
-        self.use_wq = True      # off: the bf16 kernels on the dequantised weights (tests, A/B timing)
-        if self.wq_bits is not None and self.stream_ok and self.I % 32 == 0:
-            self.pq = tuple(_PackedWQ(lib, w, self.wq_bits, key) for w, key in zip((self.wqkv, self.wo, self.wgu, self.wdown), self._keys64()))
+        self.wq_ok = self.I % 32 == 0
+        self._mods = attn_mods + (mlp.gate_proj, mlp.up_proj, mlp.down_proj)
+
+    def _srcs(self):
+        """The matrices that get packed copies (rows64 order, MX codes), in the order of ``_keys64``."""
+        return (self.wqkv, self.wo, self.wgu, self.wdown)
 
     def sync_wq(self) -> int:
-        return sum(p.sync(self.lib, w, key) for p, w, key in zip(self.pq, (self.wqkv, self.wo, self.wgu, self.wdown), self._keys64()))
+        return sum(p.sync(self.lib, w, key) for p, w, key in zip(self.pq, self._srcs(), self._keys64()))
 
     def _keys64(self):
         q, k, v, o, g, u, d = self._mods
@@ -666,7 +676,7 @@ class _FusedLayer:
         """[q|k|v], o_proj, [gate|up], down_proj in MFMA operand order (ll_rows64_pack_bf16) -- one more copy of the layer's weights,
         made the first time 17..64 sequences are decoded together; ``sync`` re-packs in place what changed at the source."""
         keys = self._keys64()
-        srcs = (self.wqkv, self.wo, self.wgu, self.wdown)
+        srcs = self._srcs()
         if self.p64 is None:
             self.p64 = tuple(_Packed64(self.lib, w, key) for w, key in zip(srcs, keys))
         elif sync:
@@ -775,9 +785,12 @@ class _FusedLayer:
         qkv = self._gemv(x, self.wqkv, self.bqkv, self.n1.weight, self.eps1, None, nqkv, H, 0, pq[0], "qkv")
         att = self._attn(qkv, nqkv, mask, cache, pe, B, h.device)
         h1 = self._gemv(att, self.wo, self.bo, None, 0.0, x, H, self.nq, 1, pq[1], "o")
-        act = self._gemv(h1, self.wgu, None, self.n2.weight, self.eps2, None, self.I, H, 2, pq[2], "gate_up")
-        h2 = self._gemv(act, self.wdown, None, None, 0.0, h1, H, self.I, 1, pq[3], "down")
-        return h2.view(B, 1, H)
+        return self._mlp(h1, pq).view(B, 1, H)
+
+    def _mlp(self, h1, pq):
+        """The MLP half on 1..16 rows of the post-attention residual stream: RMSNorm-prologue gate|up + SiLU*mul, down_proj + residual."""
+        act = self._gemv(h1, self.wgu, None, self.n2.weight, self.eps2, None, self.I, self.H, 2, pq[2], "gate_up")
+        return self._gemv(act, self.wdown, None, None, 0.0, h1, self.H, self.I, 1, pq[3], "down")
 
 
     def run_suffix(self, h, mask, cache, pe, B, S):
@@ -804,9 +817,101 @@ class _FusedLayer:
         if rc != 0:
             _lib.check(rc, name)
         h1 = self._gemv(att, self.wo, self.bo, None, 0.0, x, H, self.nq, 1, pq[1], "o")
-        act = self._gemv(h1, self.wgu, None, self.n2.weight, self.eps2, None, self.I, H, 2, pq[2], "gate_up")
-        h2 = self._gemv(act, self.wdown, None, None, 0.0, h1, H, self.I, 1, pq[3], "down")
-        return h2.view(B, S, H)
+        return self._mlp(h1, pq).view(B, S, H)
+
+
+class _MoeWorkspace:
+    """Device scratch of ``ll_moe_route_bf16`` / ``ll_moe_experts_bf16`` for up to 64 token rows, shared by the MoE layers of one model that have
+    the same sizes (they run one after the other on one stream); allocated once, so a captured graph holds a fixed address."""
+
+    def __init__(self, lib, device, E, top_k, H, I):
+        n = int(lib.ll_moe_workspace_bytes(MAX_STREAM_ROWS, E, top_k, H, I))
+        if n < 0:
+            raise ValueError(f"ll_moe_workspace_bytes: unsupported sizes E={E} top_k={top_k} H={H} I={I}")
+        self.bytes = n
+        self.t = torch.empty(n, dtype=torch.uint8, device=device)
+
+
+class _FusedMoeLayer(_FusedLayer):
+    """``_FusedLayer`` for a decoder layer whose MLP is a sparse mixture-of-experts block (Qwen3MoeSparseMoeBlock): the attention half is the
+    parent's; the MLP half is router logits (the dense Linear on mlp.gate.weight with the post-attention RMSNorm as prologue), ll_moe_route_bf16
+    and ll_moe_experts_bf16 (gate|up, down, slot sum + residual) -- eight launches per layer at 1..16 rows.  The expert and router parameters
+    are read in place: no copy, nothing for ``refresh_weight_copies`` to follow.  ``idx`` / ``w`` keep the routing of the latest call (static
+    buffers: a captured graph rewrites them at every replay)."""
+
+    def __init__(self, lib, layer, workspaces: dict):
+        self._workspaces = workspaces
+        super().__init__(lib, layer)
+
+    def _init_mlp(self, layer, attn_mods):
+        mlp = layer.mlp
+        self.experts, self.router = mlp.experts, mlp.gate
+        self.E, _, self.I = (int(v) for v in mlp.experts.down_proj.shape)
+        self.top_k, self.norm_topk = int(mlp.gate.top_k), bool(mlp.gate.norm_topk_prob)
+        self.stream_ok = self.H % 32 == 0 and self.nq % 32 == 0 and self.n1.weight.dtype == torch.bfloat16
+        self.wq_ok = True
+        self._mods = attn_mods
+        dev = mlp.gate.weight.device
+        key = (self.E, self.top_k, self.H, self.I, str(dev))
+        if key not in self._workspaces:
+            self._workspaces[key] = _MoeWorkspace(self.lib, dev, self.E, self.top_k, self.H, self.I)
+        self.ws = self._workspaces[key]
+        self.idx = torch.zeros(MAX_STREAM_ROWS, self.top_k, dtype=torch.int32, device=dev)
+        self.w = torch.zeros(MAX_STREAM_ROWS, self.top_k, dtype=torch.bfloat16, device=dev)
+
+    def _srcs(self):
+        return (self.wqkv, self.wo)
+
+    def _keys64(self):
+        q, k, v, o = self._mods
+        return (_versions(q.weight, k.weight, v.weight), _versions(o.weight))
+
+    def _router_logits(self, h1):
+        """[M, E] bf16 = F.linear(rmsnorm(h1), gate.weight): the f32-FMA GEMV up to FMA_GEMV_ROWS rows, the MFMA weight stream beyond, in
+        chunks of 16 rows (the router matrix is small and read in place: no packed copy to keep in step)."""
+        M, H, E = h1.shape[0], self.H, self.E
+        wr = self.router.weight
+        if M <= FMA_GEMV_ROWS or not self.stream_ok:
+            return self._gemv(h1, wr, None, self.n2.weight, self.eps2, None, E, H, 0)
+        out = torch.empty(M, E, dtype=torch.bfloat16, device=h1.device)
+        for r0 in range(0, M, MAX_ROWS16):
+            n = min(MAX_ROWS16, M - r0)
+            rc = self.lib.ll_linear_rows16_bf16(h1.data_ptr() + r0 * h1.stride(0) * 2, h1.stride(0), wr.data_ptr(), H, None, self.n2.weight.data_ptr(),
+                                                self.eps2, None, 0, out.data_ptr() + r0 * E * 2, E, n, E, H, 0, torch.cuda.current_stream().cuda_stream)
+            if rc != 0:
+                _lib.check(rc, "ll_linear_rows16_bf16")
+        return out
+
+    def _mlp(self, h1, pq=None):
+        """Router logits, routing, experts + residual on 1..64 rows of the un-normalised post-attention residual stream h1 [M, H]."""
+        M, H = h1.shape[0], self.H
+        stream = torch.cuda.current_stream().cuda_stream
+        logits = self._router_logits(h1)
+        rc = self.lib.ll_moe_route_bf16(logits.data_ptr(), logits.stride(0), M, self.E, self.top_k, int(self.norm_topk), self.idx.data_ptr(),
+                                        self.w.data_ptr(), self.ws.t.data_ptr(), self.ws.bytes, stream)
+        if rc != 0:
+            _lib.check(rc, "ll_moe_route_bf16")
+        out = torch.empty(M, H, dtype=torch.bfloat16, device=h1.device)
+        rc = self.lib.ll_moe_experts_bf16(h1.data_ptr(), h1.stride(0), self.n2.weight.data_ptr(), self.eps2, self.idx.data_ptr(), self.w.data_ptr(),
+                                          self.experts.gate_up_proj.data_ptr(), self.experts.down_proj.data_ptr(), h1.data_ptr(), h1.stride(0),
+                                          out.data_ptr(), H, M, self.E, self.top_k, H, self.I, self.ws.t.data_ptr(), self.ws.bytes, stream)
+        if rc != 0:
+            _lib.check(rc, "ll_moe_experts_bf16")
+        return out
+
+    def run64(self, h, mask, cache, pe, pre=None, next_norm=None):
+        """17..64 sequences: q|k|v and o_proj on the packed copies as in the parent -- o_proj without the pre-norm hand-over, the MoE calls take
+        the un-normalised h1 and the norm weight themselves -- then the MoE calls.  Returns (h_out, None): the next layer makes its own pre-norm."""
+        B, H = h.shape[0], self.H
+        x = h.view(B, H)
+        self.packed64()
+        pqkv, po = self.p64
+        xs, ssq = pre if pre is not None else _prenorm64(self.lib, x, self.n1.weight)
+        nqkv = self.nq + 2 * self.nkv_dim
+        qkv = _rows64(self.lib, xs, xs.stride(0), pqkv, self.bqkv, None, nqkv, 0, row_ssq=ssq, eps=self.eps1)
+        att = self._attn(qkv, nqkv, mask, cache, pe, B, h.device)
+        h1 = _rows64(self.lib, att, att.stride(0), po, self.bo, x, H, 1)
+        return self._mlp(h1).view(B, 1, H), None
 
 
 def _layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None, use_cache=False,
@@ -837,6 +942,48 @@ def _head_norm_declined(att) -> Optional[str]:
     return None
 
 
+MOE_MAX_EXPERTS, MOE_MAX_TOP_K, MOE_MAX_INTERMEDIATE = 256, 8, 32768       # bounds of ll_moe_route_bf16 / ll_moe_experts_bf16 (include/llamole_hip.h)
+
+
+def _is_moe_block(mlp) -> bool:
+    """Whether ``mlp`` is a mixture-of-experts block of any family (as opposed to a dense gated MLP), judged by its parts."""
+    return (hasattr(mlp, "experts") or hasattr(mlp, "shared_expert") or hasattr(mlp, "shared_experts")
+            or type(mlp).__name__.endswith(("MoeBlock", "MoE")))
+
+
+def _moe_block_declined(mlp, hidden: int) -> Optional[str]:
+    """The structural part of ``decoder_layer_declined`` for a sparse-MoE block: only the Qwen3-MoE layout is fused (softmax over all experts,
+    top-k, optional renormalisation, SiLU experts stored as [E, 2I, H] / [E, H, I], no shared expert, no biases).  Other router families
+    (Mixtral, Qwen2-MoE with a shared expert, DeepSeek) have different semantics and are named, not guessed at."""
+    kind = type(mlp).__name__
+    if kind != "Qwen3MoeSparseMoeBlock":
+        return f"MoE block of an unsupported kind ({kind})"
+    if any(getattr(mlp, a, None) is not None for a in ("shared_expert", "shared_experts", "shared_expert_gate")):
+        return "MoE block of an unsupported kind (shared expert)"
+    experts, gate = getattr(mlp, "experts", None), getattr(mlp, "gate", None)
+    wgu, wd, wr = getattr(experts, "gate_up_proj", None), getattr(experts, "down_proj", None), getattr(gate, "weight", None)
+    if not all(isinstance(t, nn.Parameter) for t in (wgu, wd, wr)) or wgu.dim() != 3 or wd.dim() != 3 or wr.dim() != 2:
+        return "MoE block of an unsupported kind (experts are not gate_up_proj [E, 2I, H] / down_proj [E, H, I] parameters with a gate.weight [E, H])"
+    E, H, I = wd.shape
+    if tuple(wgu.shape) != (E, 2 * I, H) or tuple(wr.shape) != (E, H) or H != hidden:
+        return "MoE block of an unsupported kind (experts are not gate_up_proj [E, 2I, H] / down_proj [E, H, I] parameters with a gate.weight [E, H])"
+    if not hasattr(gate, "top_k") or not hasattr(gate, "norm_topk_prob"):
+        return "MoE router without top_k / norm_topk_prob"
+    if any(getattr(m, a, None) is not None for m in (experts, gate) for a in ("bias", "gate_up_proj_bias", "down_proj_bias")):
+        return "MoE expert bias"
+    if not _is_silu(getattr(experts, "act_fn", None)):
+        return "activation is not SiLU"
+    if E > MOE_MAX_EXPERTS:
+        return f"more than {MOE_MAX_EXPERTS} experts"
+    if not 1 <= int(gate.top_k) <= min(E, MOE_MAX_TOP_K):
+        return f"top_k is not in 1..min(E, {MOE_MAX_TOP_K})"
+    if I % 8 != 0:
+        return "moe_intermediate_size is not a multiple of 8"
+    if I > MOE_MAX_INTERMEDIATE:
+        return f"moe_intermediate_size above {MOE_MAX_INTERMEDIATE}"
+    return None
+
+
 def decoder_layer_declined(layer: nn.Module) -> Optional[str]:
     """Why ``fuse_decoder_layers`` would not fuse this decoder layer (None: it would) -- the sibling of ``model_decode_declined``.  Structural
     reasons come first and dtype / device reasons last, so the layout of a model can be judged on the CPU."""
@@ -845,10 +992,15 @@ def decoder_layer_declined(layer: nn.Module) -> Optional[str]:
         return "no self_attn / mlp"
     if hasattr(layer, "_ll_fused"):
         return "already installed"
+    moe = _is_moe_block(mlp)
     if not (all(type(getattr(att, a, None)) is nn.Linear for a in ("q_proj", "k_proj", "v_proj", "o_proj"))
-            and all(type(getattr(mlp, a, None)) is nn.Linear for a in ("gate_proj", "up_proj", "down_proj"))):
+            and (moe or all(type(getattr(mlp, a, None)) is nn.Linear for a in ("gate_proj", "up_proj", "down_proj")))):
         return "projections are not plain nn.Linear"
-    if not _is_silu(getattr(mlp, "act_fn", None)):
+    if moe:
+        why = _moe_block_declined(mlp, att.q_proj.in_features)
+        if why is not None:
+            return why
+    elif not _is_silu(getattr(mlp, "act_fn", None)):
         return "activation is not SiLU"
     if not (hasattr(layer, "input_layernorm") and hasattr(layer, "post_attention_layernorm")
             and hasattr(layer.input_layernorm, "variance_epsilon")):
@@ -857,7 +1009,7 @@ def decoder_layer_declined(layer: nn.Module) -> Optional[str]:
         return "head_dim is not 64 or 128"
     if att.q_proj.in_features % 8 != 0 or att.q_proj.in_features > 8192:
         return "hidden size is not a multiple of 8 up to 8192"
-    if mlp.gate_proj.bias is not None or mlp.up_proj.bias is not None or mlp.down_proj.bias is not None:
+    if not moe and (mlp.gate_proj.bias is not None or mlp.up_proj.bias is not None or mlp.down_proj.bias is not None):
         return "MLP bias"
     if getattr(att, "sliding_window", None) is not None:
         return "sliding-window layer"
@@ -865,10 +1017,13 @@ def decoder_layer_declined(layer: nn.Module) -> Optional[str]:
     if why is not None:
         return why
     norms = [m for m in (getattr(att, "q_norm", None), getattr(att, "k_norm", None)) if m is not None]
-    if att.q_proj.weight.dtype != torch.bfloat16 or any(m.weight.dtype != torch.bfloat16 for m in norms):
+    extra = [m.weight for m in norms] + ([mlp.experts.gate_up_proj, mlp.experts.down_proj, mlp.gate.weight] if moe else [])
+    if att.q_proj.weight.dtype != torch.bfloat16 or any(t.dtype != torch.bfloat16 for t in extra):
         return "weights are not bf16"
-    if not att.q_proj.weight.is_cuda or not all(m.weight.is_cuda for m in norms):
+    if not att.q_proj.weight.is_cuda or not all(t.is_cuda for t in extra):
         return "weights are not on the device"
+    if moe and not all(t.is_contiguous() for t in extra[len(norms):]):
+        return "MoE weights are not contiguous"
     return None
 
 
@@ -881,10 +1036,11 @@ def fuse_decoder_layers(model: nn.Module) -> int:
     if layers is None:
         return 0
     n = 0
+    workspaces: dict = {}       # one MoE scratch per model and size
     for layer in layers:
         if decoder_layer_declined(layer) is not None:
             continue
-        layer._ll_fused = _FusedLayer(lib, layer)
+        layer._ll_fused = _FusedMoeLayer(lib, layer, workspaces) if _is_moe_block(layer.mlp) else _FusedLayer(lib, layer)
         layer._ll_layer_orig = layer.forward
         layer.forward = types.MethodType(_layer_forward, layer)
         n += 1
@@ -958,8 +1114,7 @@ def _model_forward(self, input_ids=None, attention_mask=None, position_ids=None,
                         h = layer._ll_fused.run(h, mask, past_key_values, pe)
                 h = self.norm(h)
                 st["served"] = True
-                from transformers.modeling_outputs import BaseModelOutputWithPast
-                return BaseModelOutputWithPast(last_hidden_state=h, past_key_values=past_key_values if use_cache else None)
+                return st["out_cls"](last_hidden_state=h, past_key_values=past_key_values if use_cache else None)
     if st.get("suffix") and input_ids is not None and inputs_embeds is None and input_ids.dim() == 2:
         out = _suffix_forward(self, st, layers, input_ids, attention_mask, position_ids, past_key_values, use_cache, kwargs)
         if out is not None:
@@ -1011,8 +1166,7 @@ def _suffix_forward(self, st, layers, input_ids, attention_mask, position_ids, c
     for layer in layers:
         h = layer._ll_fused.run_suffix(h, mask, cache, (cos, sin), B, S)
     h = self.norm(h)
-    from transformers.modeling_outputs import BaseModelOutputWithPast
-    return BaseModelOutputWithPast(last_hidden_state=h, past_key_values=cache if use_cache else None)
+    return st["out_cls"](last_hidden_state=h, past_key_values=cache if use_cache else None)
 
 
 def suffix_on_fused_layers(model: nn.Module, on: bool) -> bool:
@@ -1078,7 +1232,11 @@ def fuse_model_decode(model: nn.Module) -> bool:
         return False
     base = getattr(model, "model", model)
     rot = base.rotary_emb
-    base._ll_decode = {"lib": _lib.load(), "D": base.layers[0]._ll_fused.D}
+    import sys
+    from transformers.modeling_outputs import BaseModelOutputWithPast
+    # the output class of the base model's own forward: a MoE model's causal-LM head reads `router_logits` (None here) off it
+    out_cls = getattr(sys.modules.get(type(base).__module__), "MoeModelOutputWithPast", BaseModelOutputWithPast)
+    base._ll_decode = {"lib": _lib.load(), "D": base.layers[0]._ll_fused.D, "out_cls": out_cls}
     if rot.rope_type == "dynamic":
         base._ll_decode["dyn"] = {"max_pos": int(rot.config.max_position_embeddings), "tables": {}}
     base._ll_model_orig = base.forward
@@ -1134,6 +1292,10 @@ def accelerate_llm(model: nn.Module, linears: bool = True, fuse: bool = True, la
             all_layers = list(getattr(getattr(model, "model", model), "layers", None) or [])
             reasons = [decoder_layer_declined(l) for l in all_layers]
             info["decoder_layers_5_launches"] = fuse_decoder_layers(model)
+            n_moe = sum(isinstance(l.__dict__.get("_ll_fused"), _FusedMoeLayer) for l in all_layers)
+            if n_moe:
+                # of the fused layers, the ones whose MLP half is the MoE calls (eight launches at 1..16 rows; the key above counts them too)
+                info["moe_layers_fused"] = n_moe
             if info["decoder_layers_5_launches"] < len(all_layers):
                 info["decoder_layers_declined"] = next((r for r in reasons if r is not None), None)
             if model_decode:
@@ -1150,4 +1312,6 @@ def accelerate_llm(model: nn.Module, linears: bool = True, fuse: bool = True, la
         q["bf16_layers"] = len(fused) - q["packed_layers"]
         # token-row counts at which each matrix streams its packed codes; every other call runs the bf16 kernels on the dequantised weights
         q["packed_routes"] = {m: (sorted(WQ_ROUTES.get((bits, m), ())) if FMA_GEMV_ROWS == 2 else []) for m in WQ_MATRICES}
+        if any(_is_moe_block(getattr(l, "mlp", None)) for l in (getattr(base, "layers", None) or [])):
+            q["experts"] = "bf16"       # expert and router weights are neither rounded nor packed: only the attention Linears of a MoE layer are
     return info

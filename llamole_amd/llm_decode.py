@@ -206,6 +206,32 @@ class GraphedDecoder:
             self._eager_keys.add(self._key)
             self._graph = self._beam_graph = None
 
+    def _capture(self, attr: str, body) -> bool:
+        """Capture ``body`` (the decode step and what follows it on the device) into a new graph stored as ``self.<attr>``.  A step that the
+        installed transformers / torch cannot capture -- an op that is not permitted while a stream is capturing, e.g. the grouped GEMM of
+        HF's experts code under a sparse-MoE model whose layers are not fused -- turns this (batch, cache length) shape eager, with one
+        warning per shape, as a rotary module with a host read does; nothing of a failed capture has run on the device.  Only errors that
+        name the capture are taken this way, and only when the step ran HF's own model forward: anything else is raised."""
+        g = torch.cuda.CUDAGraph()
+        try:
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                body()
+        except Exception as e:          # noqa: BLE001 -- narrowed below: only what a capture refuses, only under HF's own step
+            # a step served by the fused prologue is all this library's launches and must capture: that failure is a bug and is raised, as is
+            # any error that does not come from the capture itself
+            if self._served_by_fused_prologue() or "captur" not in str(e).lower():
+                raise
+            import warnings
+            why = (str(e).splitlines() or [""])[0]
+            warnings.warn(f"hipGraph capture of the decode step failed ({type(e).__name__}: {why}); calls of this shape "
+                          f"({self.tok.shape[0]} rows) run eagerly (no hipGraph)")
+            self._eager_keys.add(self._key)
+            self._graph = self._beam_graph = None
+            torch.cuda.synchronize()
+            return False
+        setattr(self, attr, g)
+        return True
+
     # static buffers + captured step for a (batch, max_len) shape
     def _prepare(self, B: int, max_len: int, device, use_embeds: bool):
         from transformers import StaticCache
@@ -396,12 +422,12 @@ class GraphedDecoder:
                 mark("generate: rendezvous")
             if self._graph_on() and self._graph is None:
                 self._warm_up()                                   # the forward only, state rewound; may turn this shape's graph off
+            if self._graph_on() and self._graph is None:
+                def body():
+                    self.logits = self._step()
+                    self._hip_sample(self.logits, sp, 1)
+                self._capture("_graph", body)                     # a step that cannot be captured turns this shape eager
             if self._graph_on():
-                if self._graph is None:
-                    self._graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self._graph, capture_error_mode="thread_local"):
-                        self.logits = self._step()
-                        self._hip_sample(self.logits, sp, 1)
                 self._graph.replay()
                 logits = self.logits
             else:
@@ -523,13 +549,10 @@ class GraphedDecoder:
                 self.posid.add_(1)
             if self._graph_on() and self._graph is None:
                 self._warm_up()                                   # on a side stream, state rewound; may turn this shape's graph off
+            if self._graph_on() and self._graph is None:
+                # capture the forward once (thread-local capture: a RCCL watchdog thread polling events must not invalidate it)
+                self._capture("_graph", lambda: setattr(self, "logits", self._step()))
             if self._graph_on():
-                if self._graph is None:
-                    # capture the forward once
-                    self._graph = torch.cuda.CUDAGraph()
-                    # thread-local capture: a RCCL watchdog thread polling events must not invalidate the capture
-                    with torch.cuda.graph(self._graph, capture_error_mode="thread_local"):
-                        self.logits = self._step()
                 self._graph.replay()
                 logits = self.logits
             else:
@@ -685,13 +708,13 @@ class GraphedDecoder:
                     self.posid.add_(1)
             if self._graph_on() and self._beam_graph is None:
                 self._warm_up()                                   # the forward only, state rewound; may turn this shape's graph off
+            if self._graph_on() and self._beam_graph is None:
+                def body():
+                    self._beam_logits = self._step()
+                    if hip:
+                        self._hip_beam(self._beam_logits, p, 1, False)
+                self._capture("_beam_graph", body)
             if self._graph_on():
-                if self._beam_graph is None:
-                    self._beam_graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self._beam_graph, capture_error_mode="thread_local"):
-                        self._beam_logits = self._step()
-                        if hip:
-                            self._hip_beam(self._beam_logits, p, 1, False)
                 self._beam_graph.replay()
                 logits = self._beam_logits
             else:
