@@ -230,7 +230,8 @@ int ll_silu_mul_bf16(const void *gate, const void *up, void *out, int rows, int 
  *                     keys/values [B,nkv,maxlen,D] at positions *pos .. *pos+S-1 (pos: device int64).
  * ll_decode_attn_bf16: softmax(q K^T * scale + mask) V over the static cache with grouped-query heads; q [B,nh,S,D] strided,
  *                     mask bool [B,1,S,maxlen] (strides of dims 0 and 2), out [B,S,nh,D] contiguous; D in {64,128}, maxlen <= 16384
- *                     (LL_EINVAL beyond: a workgroup keeps the scores of all keys in LDS).  A query row without a visible key gives zeros. */
+ *                     (LL_EINVAL beyond: a workgroup keeps the scores of all keys in LDS; longer caches: ll_decode_attn_rope_split_bf16 /
+ *                     ll_suffix_attn_rope_split_bf16 below).  A query row without a visible key gives zeros. */
 int ll_kv_append_bf16(void *K, void *V, const void *k_new, const void *v_new, const int64_t *pos, int B, int nkv, int S,
                       int maxlen, int D, const int64_t *kstr, const int64_t *vstr, void *stream);
 int ll_decode_attn_bf16(const void *q, const void *K, const void *V, const void *mask, void *out, int B, int nh, int nkv, int S,
@@ -295,6 +296,37 @@ int ll_suffix_attn_rope_bf16(const void *qkv, int64_t ld_qkv, const void *cos, c
 int ll_suffix_attn_rope_qkn_bf16(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, void *Kc, void *Vc, const int64_t *pos,
                                  const void *mask, void *out, int B, int S, int nh, int nkv, int maxlen, int D, float scale,
                                  const void *q_norm_w, const void *k_norm_w, float eps, void *stream);
+/* ---- the same two calls split over the keys (flash-decoding), for static caches of up to 131072 slots ---------------------------------
+ * ll_decode_attn_rope_split_bf16 : the arguments and semantics of ll_decode_attn_rope_qkn_bf16 (q_norm_w = k_norm_w = NULL: no per-head norm,
+ *     i.e. ll_decode_attn_rope_bf16; given: eps > 0), plus a device workspace.
+ * ll_suffix_attn_rope_split_bf16 : likewise for ll_suffix_attn_rope_qkn_bf16 / ll_suffix_attn_rope_bf16 (S <= 16 new positions per sequence).
+ *     Two launches per call, both with a geometry that depends on (B, S, nh, nkv, maxlen, D) only -- *pos is read on the device, nothing
+ *     synchronises with the host, so a captured graph replays them at every position:
+ *       1. partial: the keys are cut into ranges of 512 slots; one workgroup per (range, group of query heads on one KV head, query row) writes
+ *          the maximum m, the sum of exponentials l and the un-normalised f32 output of its range to the workspace.  A group is all nh / nkv
+ *          heads of a KV head when that is 2, 4 or 7 (a K / V row is fetched once per group, for every B), one head otherwise.  A range
+ *          without a visible key costs its 512 mask bytes and contributes (m, l) = (-inf, 0).
+ *       2. combine: out = sum_r exp(m_r - M) acc_r / sum_r exp(m_r - M) l_r with M = max_r m_r, ranges with m_r = -inf left out; ONE rounding
+ *          to bf16.  A query row without a visible key gives exact zeros.  Masked slots may hold anything (NaN).
+ *     No atomics; every sum has a fixed order: the result is deterministic.  LDS per workgroup does not depend on maxlen.
+ *     Stored rows: the K / V rows written at *pos (.. *pos+S-1; rows past the last slot are dropped) are bit for bit the rows the entry points
+ *     above store (same device function for the norm, same rotary roundings), so a cache may be filled by either.  Each row is stored by one
+ *     workgroup; no workgroup reads slots *pos .. *pos+S-1 from the cache in this call: a workgroup whose range holds them rotates the new rows
+ *     itself.  Like above, the mask decides what is seen.
+ *     Bounds: D in {64,128}, nh % nkv == 0, 1 <= maxlen <= 131072 (also <= 16384, where the entry points above apply too), decode 1 <= B <= 64,
+ *     suffix 1 <= S <= 16 and B*S <= 65535, ld_qkv % 8 == 0; workspace 16-byte aligned, workspace_bytes >= ll_attn_split_workspace_bytes.
+ *     Beyond them LL_EINVAL (ll_attn_split_workspace_bytes: -1) and nothing is launched.
+ * ll_attn_split_workspace_bytes : bytes of the workspace for these sizes (decode: S = 1): B*S*nh*ceil(maxlen/512)*(D+2) f32; its layout is
+ *     private.  Calls on one stream may share one workspace. */
+int64_t ll_attn_split_workspace_bytes(int B, int S, int nh, int nkv, int maxlen, int D);
+int ll_decode_attn_rope_split_bf16(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, int64_t cs_stride, void *Kc, void *Vc,
+                                   const int64_t *pos, const void *mask, int64_t mask_stride, void *out, int B, int nh, int nkv, int maxlen,
+                                   int D, float scale, const void *q_norm_w, const void *k_norm_w, float eps, void *workspace,
+                                   int64_t workspace_bytes, void *stream);
+int ll_suffix_attn_rope_split_bf16(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, void *Kc, void *Vc, const int64_t *pos,
+                                   const void *mask, void *out, int B, int S, int nh, int nkv, int maxlen, int D, float scale,
+                                   const void *q_norm_w, const void *k_norm_w, float eps, void *workspace, int64_t workspace_bytes,
+                                   void *stream);
 /* ll_decode_prologue_dyn / ll_suffix_prologue_dyn : the two prologues for dynamic NTK rope (transformers dynamic_rope_update) without its
  *     host read of the position ids.  With L = max(position_ids of the call) + 1, read on the device by every workgroup, the frequencies are
  *     inv_freq0 [D/2] (the module's constructed original_inv_freq) while L <= max_pos (= config.max_position_embeddings) and row

@@ -32,6 +32,8 @@ MAX_STREAM_ROWS = 64    # ll_linear_rows64_bf16: up to four column blocks per we
 # stays at 2 so that two-sequence decode keeps the bit-identity with HF's op order; LLAMOLE_FMA_GEMV_ROWS=1 trades it for the 4 %)
 FMA_GEMV_ROWS = int(os.environ.get("LLAMOLE_FMA_GEMV_ROWS", "2"))
 PACK64_MIN_N = 32768    # nn.Linear modules at least this wide (lm_head) keep a packed copy for 17..64 rows
+ATTN_MAXLEN = 16384             # cache slots of ll_decode_attn_bf16 / ll_decode_attn_rope*_bf16 / ll_suffix_attn_rope*_bf16 (scores of all keys in LDS)
+ATTN_SPLIT_MAXLEN = 131072      # cache slots of the key-split entries (ll_*_attn_rope_split_bf16), taken only beyond ATTN_MAXLEN
 MAX_APPEND_ROWS = 16     # new positions per call served by the fused KV append / decode attention (decode, query tail)
 # row-parallel elementwise kernels (RMSNorm, rotary, SiLU*mul) also serve prefill-sized calls.  Round 3: the A* value estimates push
 # 256 prompts x ~144 tokens = 37 k rows through the model per forward; above the old 16 k-row limit HF's op-by-op RMSNorm (pow, mean, rsqrt,
@@ -531,7 +533,7 @@ def _decode_attention_forward(module, query, key, value, attention_mask, dropout
             and attention_mask is not None and attention_mask.dtype == torch.bool and attention_mask.dim() == 4
             and attention_mask.shape[1] == 1 and attention_mask.shape[-1] == key.shape[2] and attention_mask.stride(3) == 1
             and key.is_contiguous() and value.is_contiguous() and query.stride(3) == 1 and dropout == 0.0
-            and not torch.is_grad_enabled() and nh % key.shape[1] == 0):
+            and not torch.is_grad_enabled() and nh % key.shape[1] == 0 and key.shape[2] <= ATTN_MAXLEN):
         nkv, maxlen = key.shape[1], key.shape[2]
         out = torch.empty((B, S, nh, D), dtype=query.dtype, device=query.device)
         scale = float(scaling) if scaling is not None else D ** -0.5
@@ -615,9 +617,11 @@ class _FusedLayer:
     the weight-streaming MFMA Linear (ll_linear_rows16_bf16) -- both with the RMSNorm as prologue and the residual / SiLU*mul
     epilogues."""
 
-    def __init__(self, lib, layer):
+    def __init__(self, lib, layer, split_ws: Optional[dict] = None):
         att = layer.self_attn
         self.lib = lib
+        self._split_ws = split_ws if split_ws is not None else {}      # the model's key-split attention workspaces (_AttnSplitWorkspace), by shape
+        self._split_ok = {}                                             # (B, S, maxlen) -> whether the key-split entry takes the shape
         self.layer_idx = att.layer_idx
         q, k, v, o = att.q_proj, att.k_proj, att.v_proj, att.o_proj
         grp = getattr(q, "_ll_qkv", None) or _QKVGroup(lib, q, k, v)
@@ -695,6 +699,8 @@ class _FusedLayer:
         if not (getattr(cl, "_ll_fused_update", False) and cl.keys.dtype == torch.bfloat16 and cl.keys.is_contiguous()
                 and cl.values.is_contiguous()):
             return False
+        if not self.attn_serves(h.shape[0], 1, cl.keys.shape[2]):
+            return False
         cos = pe[0]
         return (mask.dtype == torch.bool and mask.dim() == 4 and mask.shape[1] == 1 and mask.shape[2] == 1
                 and mask.shape[3] == cl.keys.shape[2] and mask.stride(3) == 1 and cos.dtype == torch.bfloat16
@@ -735,6 +741,33 @@ class _FusedLayer:
             _lib.check(rc, "ll_gemv_fused_bf16")
         return out
 
+    def attn_serves(self, B: int, S: int, maxlen: int) -> bool:
+        """Whether this layer's attention entry points take a static cache of ``maxlen`` slots for B sequences of S new positions: up to
+        ATTN_MAXLEN the one-workgroup kernels, beyond it whatever the key-split entry accepts (its own answer, asked once per shape)."""
+        if maxlen <= ATTN_MAXLEN:
+            return True
+        key = (B, S, maxlen)
+        if key not in self._split_ok:
+            self._split_ok[key] = int(self.lib.ll_attn_split_workspace_bytes(B, S, self.nh, self.nkv, maxlen, self.D)) >= 0 and \
+                (S > 1 or B <= MAX_STREAM_ROWS)
+        return self._split_ok[key]
+
+    def _split_workspace(self, B: int, S: int, maxlen: int, device):
+        """The model's workspace of the key-split attention for this shape: allocated at the first call (the eager step that precedes a capture),
+        shared by the layers, which run one after the other on one stream; a captured graph holds its fixed address."""
+        key = (B, S, self.nh, self.nkv, maxlen, self.D, str(device))
+        ws = self._split_ws.get(key)
+        if ws is None:
+            ws = self._split_ws[key] = _AttnSplitWorkspace(self.lib, device, B, S, self.nh, self.nkv, maxlen, self.D)
+        return ws
+
+    def _split_tail(self, B: int, S: int, maxlen: int, device):
+        """The arguments the key-split entries take behind those of the *_qkn entries: norm weights (or NULL), eps, workspace, its size, stream."""
+        ws = self._split_workspace(B, S, maxlen, device)
+        qn = self.qn.weight.data_ptr() if self.qn is not None else None
+        kn = self.kn.weight.data_ptr() if self.kn is not None else None
+        return (qn, kn, self.qk_eps, ws.t.data_ptr(), ws.bytes, torch.cuda.current_stream().cuda_stream)
+
     def _attn(self, qkv, nqkv, mask, cache, pe, B, device):
         cl = cache.layers[self.layer_idx]
         pos = cache.layers[0].cumulative_length
@@ -743,7 +776,10 @@ class _FusedLayer:
         args = (qkv.data_ptr(), nqkv, cos.data_ptr(), sin.data_ptr(), 0 if cos.shape[0] == 1 else cos.stride(0), cl.keys.data_ptr(),
                 cl.values.data_ptr(), pos.data_ptr(), mask.data_ptr(), mask.stride(0), att.data_ptr(), B, self.nh, self.nkv,
                 cl.keys.shape[2], self.D, self.scaling)
-        if self.qn is not None:
+        if cl.keys.shape[2] > ATTN_MAXLEN:        # beyond the one-workgroup kernels: the keys split over workgroups, two launches
+            name = "ll_decode_attn_rope_split_bf16"
+            rc = self.lib.ll_decode_attn_rope_split_bf16(*args, *self._split_tail(B, 1, cl.keys.shape[2], device))
+        elif self.qn is not None:
             name = "ll_decode_attn_rope_qkn_bf16"
             rc = self.lib.ll_decode_attn_rope_qkn_bf16(*args, self.qn.weight.data_ptr(), self.kn.weight.data_ptr(), self.qk_eps,
                                                        torch.cuda.current_stream().cuda_stream)
@@ -807,7 +843,10 @@ class _FusedLayer:
         att = torch.empty(R, self.nq, dtype=torch.bfloat16, device=h.device)
         args = (qkv.data_ptr(), nqkv, cos.data_ptr(), sin.data_ptr(), cl.keys.data_ptr(), cl.values.data_ptr(), pos.data_ptr(), mask.data_ptr(),
                 att.data_ptr(), B, S, self.nh, self.nkv, cl.keys.shape[2], self.D, self.scaling)
-        if self.qn is not None:
+        if cl.keys.shape[2] > ATTN_MAXLEN:
+            name = "ll_suffix_attn_rope_split_bf16"
+            rc = self.lib.ll_suffix_attn_rope_split_bf16(*args, *self._split_tail(B, S, cl.keys.shape[2], h.device))
+        elif self.qn is not None:
             name = "ll_suffix_attn_rope_qkn_bf16"
             rc = self.lib.ll_suffix_attn_rope_qkn_bf16(*args, self.qn.weight.data_ptr(), self.kn.weight.data_ptr(), self.qk_eps,
                                                        torch.cuda.current_stream().cuda_stream)
@@ -818,6 +857,18 @@ class _FusedLayer:
             _lib.check(rc, name)
         h1 = self._gemv(att, self.wo, self.bo, None, 0.0, x, H, self.nq, 1, pq[1], "o")
         return self._mlp(h1, pq).view(B, S, H)
+
+
+class _AttnSplitWorkspace:
+    """Device scratch of ``ll_decode_attn_rope_split_bf16`` / ``ll_suffix_attn_rope_split_bf16`` (per-range softmax statistics and partial
+    outputs) for one shape; one per model and shape, allocated once, so a captured graph holds a fixed address."""
+
+    def __init__(self, lib, device, B, S, nh, nkv, maxlen, D):
+        n = int(lib.ll_attn_split_workspace_bytes(B, S, nh, nkv, maxlen, D))
+        if n < 0:
+            raise ValueError(f"ll_attn_split_workspace_bytes: unsupported sizes B={B} S={S} nh={nh} nkv={nkv} maxlen={maxlen} D={D}")
+        self.bytes = n
+        self.t = torch.empty(n, dtype=torch.uint8, device=device)
 
 
 class _MoeWorkspace:
@@ -839,9 +890,9 @@ class _FusedMoeLayer(_FusedLayer):
     are read in place: no copy, nothing for ``refresh_weight_copies`` to follow.  ``idx`` / ``w`` keep the routing of the latest call (static
     buffers: a captured graph rewrites them at every replay)."""
 
-    def __init__(self, lib, layer, workspaces: dict):
+    def __init__(self, lib, layer, workspaces: dict, split_ws: Optional[dict] = None):
         self._workspaces = workspaces
-        super().__init__(lib, layer)
+        super().__init__(lib, layer, split_ws)
 
     def _init_mlp(self, layer, attn_mods):
         mlp = layer.mlp
@@ -1037,10 +1088,12 @@ def fuse_decoder_layers(model: nn.Module) -> int:
         return 0
     n = 0
     workspaces: dict = {}       # one MoE scratch per model and size
+    split_ws: dict = {}         # one key-split attention scratch per model and shape (caches beyond ATTN_MAXLEN slots)
     for layer in layers:
         if decoder_layer_declined(layer) is not None:
             continue
-        layer._ll_fused = _FusedMoeLayer(lib, layer, workspaces) if _is_moe_block(layer.mlp) else _FusedLayer(lib, layer)
+        layer._ll_fused = (_FusedMoeLayer(lib, layer, workspaces, split_ws) if _is_moe_block(layer.mlp)
+                           else _FusedLayer(lib, layer, split_ws))
         layer._ll_layer_orig = layer.forward
         layer.forward = types.MethodType(_layer_forward, layer)
         n += 1
@@ -1067,6 +1120,7 @@ def _model_forward(self, input_ids=None, attention_mask=None, position_ids=None,
     create_causal_mask), the five-launch layers, final norm.  Anything else goes to the original forward."""
     st = self._ll_decode
     st["served"] = False          # whether this call ran on the fused path (GraphedDecoder reads it after its eager warm-up step)
+    st["declined"] = None         # why a decode-shaped call on a long static cache went to HF's layers instead (the reason, for this call)
     layers = self.layers[: self.config.num_hidden_layers]
     if (input_ids is not None and inputs_embeds is None and input_ids.dim() == 2 and input_ids.shape[1] == 1
             and input_ids.shape[0] <= MAX_STREAM_ROWS and input_ids.is_cuda and not torch.is_grad_enabled() and past_key_values is not None
@@ -1075,7 +1129,8 @@ def _model_forward(self, input_ids=None, attention_mask=None, position_ids=None,
             and position_ids.dtype == torch.long and not kwargs.get("output_hidden_states") and not kwargs.get("output_attentions")
             and getattr(past_key_values, "layers", None) and all(getattr(l, "_ll_fused_update", False) for l in past_key_values.layers)
             and attention_mask.shape[1] == past_key_values.layers[0].keys.shape[2]
-            and past_key_values.layers[0].keys.dtype == torch.bfloat16):
+            and past_key_values.layers[0].keys.dtype == torch.bfloat16
+            and layers[0]._ll_fused.attn_serves(input_ids.shape[0], 1, attention_mask.shape[1])):
         B, maxlen, D = input_ids.shape[0], attention_mask.shape[1], st["D"]
         dev = input_ids.device
         h = self.embed_tokens(input_ids)
@@ -1120,6 +1175,13 @@ def _model_forward(self, input_ids=None, attention_mask=None, position_ids=None,
         if out is not None:
             st["served"] = True
             return out
+    clayers = getattr(past_key_values, "layers", None)
+    keys = getattr(clayers[0], "keys", None) if clayers else None
+    if input_ids is not None and input_ids.dim() == 2 and input_ids.shape[1] <= MAX_APPEND_ROWS and keys is not None and keys.dim() == 4 \
+            and keys.shape[2] > ATTN_MAXLEN \
+            and not layers[0]._ll_fused.attn_serves(input_ids.shape[0], input_ids.shape[1], keys.shape[2]):
+        st["declined"] = (f"decoder_layers: a static cache of {keys.shape[2]} slots ({input_ids.shape[0]} x {input_ids.shape[1]} new positions) is "
+                          f"outside the bounds of the key-split attention (at most {ATTN_SPLIT_MAXLEN} slots, {MAX_STREAM_ROWS} sequences at decode)")
     return self._ll_model_orig(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
                                past_key_values=past_key_values, inputs_embeds=inputs_embeds, use_cache=use_cache, **kwargs)
 
@@ -1139,7 +1201,7 @@ def _suffix_forward(self, st, layers, input_ids, attention_mask, position_ids, c
             and clayers[0].keys.is_contiguous() and clayers[0].values.is_contiguous() and clayers[0].keys.shape[0] == B
             and position_ids is not None and position_ids.shape == input_ids.shape and position_ids.dtype == torch.long
             and not kwargs.get("output_hidden_states") and not kwargs.get("output_attentions")
-            and all(l._ll_fused.stream_ok for l in layers)):
+            and all(l._ll_fused.stream_ok for l in layers) and layers[0]._ll_fused.attn_serves(B, S, attention_mask.shape[1])):
         return None
     h = self.embed_tokens(input_ids)
     if h.dtype != torch.bfloat16 or not h.is_contiguous():
@@ -1292,6 +1354,8 @@ def accelerate_llm(model: nn.Module, linears: bool = True, fuse: bool = True, la
             all_layers = list(getattr(getattr(model, "model", model), "layers", None) or [])
             reasons = [decoder_layer_declined(l) for l in all_layers]
             info["decoder_layers_5_launches"] = fuse_decoder_layers(model)
+            # static caches beyond ATTN_MAXLEN slots stay fused up to this many (the key-split attention entries); longer ones run HF's layers
+            info["long_cache_attention_max_slots"] = ATTN_SPLIT_MAXLEN
             n_moe = sum(isinstance(l.__dict__.get("_ll_fused"), _FusedMoeLayer) for l in all_layers)
             if n_moe:
                 # of the fused layers, the ones whose MLP half is the MoE calls (eight launches at 1..16 rows; the key above counts them too)
