@@ -1,15 +1,16 @@
-// Shared body of the two decode-attention kernels (llm_ops.hip: ll_decode_attn_bf16; llm_layer.hip: the fused
-// rope + append + attention).  One workgroup (ATTN_WAVES waves) per (query head, sequence[, query position]).
+// Shared pieces of the decode-attention kernels: the geometry, the loads and the dot / axpy / fold steps that the one-workgroup kernels of
+// llm_attn.hip and the key-split kernels of llm_attn_split.hip have in common, and the whole body (attn_prefetch + attn_finish) of the per-head
+// kernels of llm_attn.hip -- one workgroup (ATTN_WAVES waves) per (query head, sequence[, query position]).
 //
 // Access pattern: a wave-level load instruction covers RPI = 1024/(2 D) whole key (or value) rows -- LPR = D/8 lanes x 16 B
 // per row, fully coalesced -- so a tile of 256 keys is 64/RPI load instructions per wave for K and as many for V.
 //   scores: lane (r, c) holds q[8c..8c+7] in registers and dots it with its 16 B of key row 4i + r; a DPP reduction over
 //           the LPR lanes of the row finishes the dot product (no LDS traffic, no per-thread row walks);
 //   P.V   : the same lanes accumulate p[row] * v[row][8c..8c+7] over the rows they see; the RPI row groups are combined
-//           through LDS at the end.
+//           through LDS (per-head body) or across lanes (attn_fold_rows) at the end.
 // The first tile -- the whole context of a short prompt -- is requested BEFORE anything else is computed (K, V and mask:
 // one memory round trip that overlaps the query preparation: rotary embedding, cache append).  Softmax statistics in f32.
-// Both kernels share this code, so the fused layer stays bit-identical to the op-by-op path.
+// The per-head kernels share attn_finish, so the fused layer stays bit-identical to the op-by-op path.
 #pragma once
 #include "common.h"
 
@@ -22,11 +23,12 @@ typedef uint32_t au32x4 __attribute__((ext_vector_type(4)));
 constexpr int ATTN_WAVES = 8;
 constexpr int ATTN_THREADS = ATTN_WAVES * 64;
 constexpr int ATTN_PART_FLOATS = ATTN_WAVES * 512;      // [waves][rows per load][D]: RPI * D = 512 for either D
+constexpr int ATTN_MAX_KEYS = 16384;                    // the keys whose scores fit one workgroup's LDS (longer caches: llm_attn_split.hip)
 
-template <int D> struct AttnGeom {
+template <int D, int W = ATTN_WAVES> struct AttnGeom {     // W waves per workgroup
     static constexpr int LPR = D / 8;                      // lanes per row (16 B each)
     static constexpr int RPI = 64 / LPR;                   // rows per wave-level load instruction
-    static constexpr int KPW = 256 / ATTN_WAVES;           // keys per wave of a 256-key tile
+    static constexpr int KPW = 256 / W;                    // keys per wave of a 256-key tile
     static constexpr int NI = KPW / RPI;                   // instructions per wave for its keys of a tile
 };
 
@@ -37,8 +39,8 @@ template <int D> struct AttnTile0 {
 };
 
 // key index handled by (wave, instruction i, lane) inside a tile starting at j0
-template <int D> __device__ __forceinline__ int attn_key(int j0, int wave, int i, int lane) {
-    return j0 + wave * AttnGeom<D>::KPW + i * AttnGeom<D>::RPI + lane / AttnGeom<D>::LPR;
+template <int D, int W = ATTN_WAVES> __device__ __forceinline__ int attn_key(int j0, int wave, int i, int lane) {
+    return j0 + wave * AttnGeom<D, W>::KPW + i * AttnGeom<D, W>::RPI + lane / AttnGeom<D, W>::LPR;
 }
 
 template <int D>
@@ -85,6 +87,20 @@ __device__ __forceinline__ void attn_axpy8(float (&acc)[8], float p, au32x4 vv) 
     acc[5] = fmaf(p, __uint_as_float(vv[2] & 0xffff0000u), acc[5]);
     acc[6] = fmaf(p, __uint_as_float(vv[3] << 16), acc[6]);
     acc[7] = fmaf(p, __uint_as_float(vv[3] & 0xffff0000u), acc[7]);
+}
+
+// P.V partials of G heads, lane (r, c) holding columns 8c..8c+7 of the rows it saw: the RPI row groups of a wave are summed across lanes (xor LPR,
+// 2 LPR, ...), after which every lane holds the wave's partial of its columns
+template <int D, int G> __device__ __forceinline__ void attn_fold_rows(float (&acc)[G][8]) {
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float v = acc[g][e];
+#pragma unroll
+            for (int off = AttnGeom<D>::LPR; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+            acc[g][e] = v;
+        }
 }
 
 // qs [D] f32 query, part [ATTN_WAVES][RPI][D], sc [maxlen], red [2 * ATTN_WAVES] in LDS; the caller has synchronised after writing qs (and kn /

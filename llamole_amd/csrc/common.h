@@ -47,6 +47,17 @@ void set_error(const char *fmt, ...);
         if (rc__ != 0) return rc__; \
     } while (0)
 
+// A launch with more than 64 KB of dynamic LDS needs the kernel's hipFuncAttributeMaxDynamicSharedMemorySize raised first.  One high-water
+// mark per kernel: the attribute is set only by a launch that asks for more than 64 KB and more than any launch of that kernel before it.
+template <auto Kernel> inline int allow_dynamic_lds(size_t lds) {
+    static size_t mark = 64 * 1024;
+    if (lds > mark) {
+        LL_HIP(hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        mark = lds;
+    }
+    return LL_OK;
+}
+
 // Debug allocation mode of the engines' device buffers (env LL_DEBUG_POISON=1; off = plain zero-filled allocations): the payload starts as
 // 0xFF bytes (NaN / -1) and LL_GUARD_BYTES of 0xA5 follow it; `debug_guard_check` (buffer growth / release) reports any byte a kernel wrote
 // past the end on stderr and aborts -- the GPU test suite run in this mode is the out-of-bounds hunt (no GPU AddressSanitizer on this pool).

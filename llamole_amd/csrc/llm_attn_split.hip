@@ -12,7 +12,8 @@
 // statistics.  LDS per workgroup does not depend on maxlen (static, <= 54 KB).  No atomics: every sum has a fixed order.
 //
 // The new rows: cache slots *pos .. *pos+S-1 are read by NOBODY in this launch.  Every workgroup whose range holds such a slot rotates those rows
-// itself (same head_pair, same roundings as decode_attn_rope_kernel / suffix_attn_rope_kernel) into LDS and takes keys and values from there; the
+// itself (head_pair and rope_pair of head_pair.h under head_row_rotated's lane rule, spelled out in the role loop: the arithmetic of
+// decode_attn_rope_kernel / suffix_attn_rope_kernel in llm_attn.hip) into LDS and takes keys and values from there; the
 // row of slot *pos + t is stored to the cache by exactly one workgroup: the one of query row s = t, of the first head group of the KV head, whose
 // range holds the slot.
 #include "common.h"
@@ -28,16 +29,6 @@ constexpr int SPLIT_MAX_RANGES = SPLIT_MAXLEN / SPLIT_RANGE;       // 256
 constexpr int SPLIT_MAX_S = 16;
 constexpr int COMBINE_THREADS = 512;
 static_assert(SPLIT_RANGE == ATTN_THREADS, "one mask byte and one score per thread");
-
-// rotary embedding of the pair (x1, x2) a lane < D/2 holds: the arithmetic of decode_attn_rope_kernel, every product and the sum rounded to bf16
-template <int D>
-__device__ __forceinline__ void rope_pair(float x1, float x2, const bf16_t *c, const bf16_t *sv, int lane, float &y1, float &y2) {
-    constexpr int half = D / 2;
-    const float c1 = bf16_to_f32(c[lane]), c2 = bf16_to_f32(c[lane + half]);
-    const float s1 = bf16_to_f32(sv[lane]), s2 = bf16_to_f32(sv[lane + half]);
-    y1 = bfr2(x1 * c1) + bfr2(-x2 * s1);
-    y2 = bfr2(x2 * c2) + bfr2(x1 * s2);
-}
 
 // qkv rows r (stride ld_qkv), cos / sin rows r (stride cs0: 0 broadcasts), mask rows r (stride ms0), r = b*S + s; query row s sits at slot *pos + s.
 // ml [rows][nh][nr][2] f32 (m, l), acc [rows][nh][nr][D] f32.
@@ -218,15 +209,7 @@ __global__ __launch_bounds__(ATTN_THREADS) void attn_split_partial_kernel(const 
         }
     }
     // the RPI row groups of a wave are combined across lanes (xor LPR, 2 LPR, ...), the waves through LDS
-#pragma unroll
-    for (int g = 0; g < GT; ++g)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float a = acc[g][e];
-#pragma unroll
-            for (int o = LPR; o < 64; o <<= 1) a += __shfl_xor(a, o, 64);
-            acc[g][e] = a;
-        }
+    attn_fold_rows<D, GT>(acc);
     if (rr == 0) {
 #pragma unroll
         for (int g = 0; g < GT; ++g)

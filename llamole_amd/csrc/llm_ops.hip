@@ -8,8 +8,9 @@
 //                     -> to(bf16) -> weight * x)
 //   ll_rope_bf16      apply_rotary_pos_emb: q*cos + rotate_half(q)*sin for q and k (strided [B,h,S,d] views)
 //   ll_silu_mul_bf16  act_fn(gate) * up of the gated MLP
+//   ll_kv_append_bf16 StaticLayer.update: the new key / value rows into the static cache
+// The attention over that cache is llm_attn.hip's.
 #include "common.h"
-#include "attn_decode.h"
 
 namespace ll {
 
@@ -126,36 +127,6 @@ __global__ __launch_bounds__(64) void kv_append_bf16_kernel(bf16_t *__restrict__
     }
 }
 
-// Decode attention over a static KV cache (GQA): one workgroup per (query head, batch*query position).
-//   scores_j = q . K[j] * scale for keys with mask[b,0,s,j] true; softmax in f32; out = sum_j p_j V[j].
-// Replaces repeat_kv (two full-cache copies) + SDPA + mask fills of the HF sdpa path at decode.  D in {64, 128}.
-// Body in attn_decode.h (shared with the fused rope + append + attention kernel of llm_layer.hip).
-template <int D>
-__global__ __launch_bounds__(ATTN_THREADS) void decode_attn_bf16_kernel(const bf16_t *__restrict__ q, const bf16_t *__restrict__ K,
-                                                               const bf16_t *__restrict__ V, const unsigned char *__restrict__ mask,
-                                                               bf16_t *__restrict__ out, int nh, int nkv, int S, int maxlen,
-                                                               float scale, int64_t qs0, int64_t qs1, int64_t qs2,
-                                                               int64_t ms0, int64_t ms2) {
-    extern __shared__ __attribute__((aligned(16))) float sm_attn[];
-    float *qs = sm_attn;                 // [D]     query in f32 (16-B aligned LDS broadcast reads)
-    float *part = qs + D;                // [waves][rows per load][D] partial outputs = ATTN_PART_FLOATS for either D
-    float *sc = part + ATTN_PART_FLOATS; // [maxlen] scores -> probabilities
-    __shared__ float red[2 * ATTN_WAVES];
-    const int h = blockIdx.x, bs = blockIdx.y;
-    const int b = bs / S, s = bs - b * S;
-    const int kvh = h / (nh / nkv);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bf16_t *Kb = K + ((int64_t)b * nkv + kvh) * maxlen * D;
-    const bf16_t *Vb = V + ((int64_t)b * nkv + kvh) * maxlen * D;
-    const unsigned char *mrow = mask + b * ms0 + s * ms2;
-    AttnTile0<D> t0;
-    attn_prefetch<D>(t0, Kb, Vb, mrow, maxlen, tid, lane, wave);
-    if (tid < D) qs[tid] = bf16_to_f32(q[b * qs0 + h * qs1 + s * qs2 + tid]);
-    __syncthreads();
-    attn_finish<D, false>(t0, qs, part, sc, red, Kb, Vb, mrow, maxlen, -1, nullptr, nullptr, scale,
-                          out + (((int64_t)b * S + s) * nh + h) * D, tid, lane, wave);
-}
-
 }  // namespace ll
 
 using namespace ll;
@@ -202,29 +173,6 @@ int ll_kv_append_bf16(void *K, void *V, const void *k_new, const void *v_new, co
     hipLaunchKernelGGL(kv_append_bf16_kernel, dim3(B * nkv * S), dim3(64), 0, (hipStream_t)stream, (bf16_t *)K, (bf16_t *)V,
                        (const bf16_t *)k_new, (const bf16_t *)v_new, (const long long *)pos, nkv, S, maxlen, D, kstr[0], kstr[1],
                        kstr[2], vstr[0], vstr[1], vstr[2]);
-    LL_LAUNCH_CHECK();
-    return LL_OK;
-}
-
-int ll_decode_attn_bf16(const void *q, const void *K, const void *V, const void *mask, void *out, int B, int nh, int nkv, int S,
-                        int maxlen, int D, float scale, const int64_t *qstr, const int64_t *mstr, void *stream) {
-    LL_CHECK(q && K && V && mask && out && qstr && mstr, "null argument");
-    LL_CHECK((D == 64 || D == 128) && nh % nkv == 0 && maxlen >= 1 && maxlen <= 16384, "ll_decode_attn_bf16: unsupported shape");
-    const size_t lds = ((size_t)maxlen + D + ATTN_PART_FLOATS) * 4;
-    dim3 grid(nh, B * S);
-#define LL_ATTN(D_)                                                                                                                      \
-    do {                                                                                                                                 \
-        static size_t attr = 64 * 1024;       /* > 64 KB of dynamic LDS (maxlen > ~12 k keys) needs the attribute */                    \
-        if (lds > attr) {                                                                                                                \
-            LL_HIP(hipFuncSetAttribute((const void *)decode_attn_bf16_kernel<D_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            attr = lds;                                                                                                                  \
-        }                                                                                                                                \
-        hipLaunchKernelGGL((decode_attn_bf16_kernel<D_>), grid, dim3(ATTN_THREADS), lds, (hipStream_t)stream, (const bf16_t *)q,         \
-                           (const bf16_t *)K, (const bf16_t *)V, (const unsigned char *)mask, (bf16_t *)out, nh, nkv, S, maxlen, scale,  \
-                           qstr[0], qstr[1], qstr[2], mstr[0], mstr[1]);                                                                 \
-    } while (0)
-    if (D == 128) LL_ATTN(128); else LL_ATTN(64);
-#undef LL_ATTN
     LL_LAUNCH_CHECK();
     return LL_OK;
 }

@@ -209,11 +209,7 @@ static int launch_rows16_seg(int waves, int ksplit, hipStream_t s, const bf16_t 
     const int ntiles = (N + 15) / 16;
     const size_t lds = (size_t)waves * (NT + 1) * 16 * (SEG + 16);
     LL_CHECK(lds <= 160 * 1024, "ll_linear_rows16_bf16: %d waves x %d-byte segments need %zu bytes of LDS", waves, SEG, lds);
-    static size_t attr_lds = 0;       // > 64 KB of dynamic LDS needs the attribute
-    if (lds > attr_lds) {
-        LL_HIP(hipFuncSetAttribute((const void *)rows16_kernel<EPI, SEG, NORM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds = lds;
-    }
+    LL_TRY((allow_dynamic_lds<rows16_kernel<EPI, SEG, NORM>>(lds)));
     const int tpw = waves / ksplit;
     hipLaunchKernelGGL((rows16_kernel<EPI, SEG, NORM>), dim3((ntiles + tpw - 1) / tpw), dim3(waves * 64), lds, s, X, ldx, W, ldw, bias, normw,
                        eps, res, ldr, C, ldc, M, N, K, ksplit, out_f32);

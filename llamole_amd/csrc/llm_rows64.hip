@@ -353,11 +353,7 @@ template <int EPI, int MB, int KS>
 static int launch_rows64_ks(int ksg, hipStream_t s, const bf16_t *X, int ldx, const bf16_t *Wp, const float *bias, const bf16_t *res, int ldr,
                             bf16_t *C, int ldc, float *slab, const float *row_ssq, int ssq_chunks, float eps, int M, int N, int K) {
     const size_t lds = (size_t)2 * MB * 16 * (KS * 2 + 16);
-    static bool attr_set = false;
-    if (!attr_set) {
-        LL_HIP(hipFuncSetAttribute((const void *)rows64_kernel<EPI, MB, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
+    LL_TRY((allow_dynamic_lds<rows64_kernel<EPI, MB, KS>>(lds)));
     const int tiles_n = (N + 15) / 16;
     const int groups = EPI == R64_SILU_MUL ? cdiv(tiles_n, 2) : cdiv(tiles_n, 4);
     const int units = groups * ksg;

@@ -344,11 +344,7 @@ static int launch_gemv_wq(hipStream_t s, const bf16_t *X, int ldx, const unsigne
                           const bf16_t *normw, float eps, const bf16_t *res, int ldr, bf16_t *C, int ldc, int N, int K) {
     constexpr int EPC = 128 / BITS, P = EPC / 8;
     const size_t lds = (size_t)MROWS * ((K / EPC + 63) / 64) * 64 * P * 16;
-    static size_t attr_lds = 0;       // > 64 KB of dynamic LDS needs the attribute
-    if (lds > 65536 && lds > attr_lds) {
-        LL_HIP(hipFuncSetAttribute((const void *)gemv_wq_kernel<BITS, MROWS, NORM, EPI, XC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds = lds;
-    }
+    LL_TRY((allow_dynamic_lds<gemv_wq_kernel<BITS, MROWS, NORM, EPI, XC>>(lds)));
     const dim3 grid(EPI == WQ_SILU_MUL ? cdiv(N, 4) : cdiv(N, 8));
     hipLaunchKernelGGL((gemv_wq_kernel<BITS, MROWS, NORM, EPI, XC>), grid, dim3(256), lds, s, X, ldx, codes, scales, bias, normw, eps, res, ldr, C,
                        ldc, N, K);
@@ -611,11 +607,7 @@ static int launch_rows16_wq_seg(int waves, int ksplit, hipStream_t s, const bf16
     const int ntiles = (N + 15) / 16;
     const size_t lds = rows16_wq_lds(BITS, CSEG, waves, NT);
     LL_CHECK(lds <= 160 * 1024, "ll_linear_rows16_wq: %d waves x %d-byte code segments at %d bits need %zu bytes of LDS", waves, CSEG, BITS, lds);
-    static size_t attr_lds = 0;       // > 64 KB of dynamic LDS needs the attribute
-    if (lds > attr_lds) {
-        LL_HIP(hipFuncSetAttribute((const void *)rows16_wq_kernel<EPI, BITS, CSEG, NORM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds = lds;
-    }
+    LL_TRY((allow_dynamic_lds<rows16_wq_kernel<EPI, BITS, CSEG, NORM>>(lds)));
     const int tpw = waves / ksplit;
     hipLaunchKernelGGL((rows16_wq_kernel<EPI, BITS, CSEG, NORM>), dim3((ntiles + tpw - 1) / tpw), dim3(waves * 64), lds, s, X, ldx, codes, scales,
                        bias, normw, eps, res, ldr, C, ldc, M, N, K, ksplit);

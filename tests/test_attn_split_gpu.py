@@ -134,7 +134,7 @@ def test_split_decode_20_sequences(lib):
         check_decode(lib, SC.decode_case(64, 4, 2, SC.LONG, SC.LONG - 1, v, B=20))
 
 
-@pytest.mark.parametrize("D,nh,nkv", [(128, 8, 2), (64, 7, 1)])
+@pytest.mark.parametrize("D,nh,nkv", [(128, 8, 2), (64, 7, 1), (64, 4, 2)])
 def test_split_decode_with_head_norms(lib, D, nh, nkv):
     """q_norm_w / k_norm_w given: the Qwen3 layout against tests/qknorm_reference.py (tie-safe head vectors: the stored key bit for bit)"""
     for pos in (SC.RANGE - 1, SC.RANGE, SC.SMALL - 1):
@@ -164,22 +164,30 @@ def test_split_and_one_workgroup_entry_store_the_same_rows(lib, D, nh, nkv, maxl
 
 
 # ------------------------------------------------------------------------------------------------------------------ suffix
+def run_suffix(lib, c, Kc, Vc, cos, sin, mask, entry="ll_suffix_attn_rope_split_bf16"):
+    """one ll_suffix_attn_rope_split_bf16 call behind ll_suffix_prologue's cos / sin / mask; returns out [B*S, nh*D]"""
+    qkv = c.qkv.cuda()
+    pos = torch.tensor([c.pos], dtype=torch.long, device="cuda")
+    ws, n = _workspace(lib, c.B, c.S, c)
+    out = _nan(c.B * c.S, c.nh * c.D)
+    _check(lib.ll_suffix_attn_rope_split_bf16(qkv.data_ptr(), c.ld_qkv, cos.data_ptr(), sin.data_ptr(), Kc.data_ptr(), Vc.data_ptr(),
+                                              pos.data_ptr(), mask.data_ptr(), out.data_ptr(), c.B, c.S, c.nh, c.nkv, c.maxlen, c.D, c.scale,
+                                              *_norm_args(c), ws.data_ptr(), n, _stream()), entry)
+    torch.cuda.synchronize()
+    return out
+
+
 def check_suffix(lib, c, entry="ll_suffix_attn_rope_split_bf16", expected=R.suffix_expected):
     B, S, nh, D, L, rows = c.B, c.S, c.nh, c.D, c.maxlen, c.B * c.S
     Kp, Vp = R.poison(c, c.K0, c.V0, c.old)
     Kc, Vc = Kp.cuda(), Vp.cuda()
-    posid, freq, mask2d, qkv = c.position_ids.cuda(), c.inv_freq.cuda(), c.mask2d.cuda(), c.qkv.cuda()
+    posid, freq, mask2d = c.position_ids.cuda(), c.inv_freq.cuda(), c.mask2d.cuda()
     pos = torch.tensor([c.pos], dtype=torch.long, device="cuda")
     cos, sin = _nan(rows, D), _nan(rows, D)
     mask = torch.ones(rows, L, dtype=torch.bool, device="cuda")
     _check(lib.ll_suffix_prologue(posid.data_ptr(), freq.data_ptr(), 1.0, mask2d.data_ptr(), c.mask2d_stride, pos.data_ptr(), cos.data_ptr(),
                                   sin.data_ptr(), mask.data_ptr(), B, S, D, L, _stream()), "ll_suffix_prologue")
-    ws, n = _workspace(lib, B, S, c)
-    out = _nan(rows, nh * D)
-    _check(lib.ll_suffix_attn_rope_split_bf16(qkv.data_ptr(), c.ld_qkv, cos.data_ptr(), sin.data_ptr(), Kc.data_ptr(), Vc.data_ptr(),
-                                              pos.data_ptr(), mask.data_ptr(), out.data_ptr(), B, S, nh, c.nkv, L, D, c.scale, *_norm_args(c),
-                                              ws.data_ptr(), n, _stream()), entry)
-    torch.cuda.synchronize()
+    out = run_suffix(lib, c, Kc, Vc, cos, sin, mask, entry)
     inputs, written = expected(c, cos.cpu().view(B, S, D), sin.cpu().view(B, S, D))
     ref, absref = R.reference(c, inputs)
     Kp[:, :, written], Vp[:, :, written] = inputs[1][:, :, written], inputs[2][:, :, written]

@@ -57,11 +57,8 @@ def _same_bits(entry, c, got, want, what):
 
 
 # ------------------------------------------------------------------------------------------------------------------ ll_decode_attn_rope_bf16
-def check_decode(lib, c, entry):
-    keep = c.visible.clone()
-    keep[:, c.pos] = False                                       # the stale row at *pos
-    Kp, Vp = R.poison(c, c.K0, c.V0, keep)
-    Kc, Vc = Kp.cuda(), Vp.cuda()
+def run_decode(lib, c, Kc, Vc):
+    """one ll_decode_attn_rope_bf16 call on the case's inputs; returns out [B, nh*D]"""
     qkv, cos, sin, mask = c.qkv.cuda(), c.cos.cuda(), c.sin.cuda(), c.mask.cuda()
     pos = torch.tensor([c.pos], dtype=torch.long, device="cuda")
     out = _nan(c.B, c.nh * c.D)
@@ -69,6 +66,15 @@ def check_decode(lib, c, entry):
                                         pos.data_ptr(), mask.data_ptr(), c.mask_stride, out.data_ptr(), c.B, c.nh, c.nkv, c.maxlen, c.D,
                                         c.scale, _stream()), "ll_decode_attn_rope_bf16")
     torch.cuda.synchronize()
+    return out
+
+
+def check_decode(lib, c, entry):
+    keep = c.visible.clone()
+    keep[:, c.pos] = False                                       # the stale row at *pos
+    Kp, Vp = R.poison(c, c.K0, c.V0, keep)
+    Kc, Vc = Kp.cuda(), Vp.cuda()
+    out = run_decode(lib, c, Kc, Vc)
     inputs, (k_rot, v_new) = R.decode_expected(c)
     ref, absref = R.reference(c, inputs)
     Kp[:, :, c.pos], Vp[:, :, c.pos] = k_rot, v_new              # the appended row, every other slot as it was
@@ -117,11 +123,9 @@ def test_decode_attn_rope_grouped_lds_switch(lib, maxlen, variant):
 
 
 # ------------------------------------------------------------------------------------------------------------------ ll_decode_attn_bf16
-def check_attn(lib, c):
-    entry = "ll_decode_attn_bf16"
+def run_attn(lib, c, Kc, Vc):
+    """one ll_decode_attn_bf16 call on the case's inputs (q a strided view, padded mask rows); returns out [B, S, nh, D]"""
     B, S, nh, D, L = c.B, c.S, c.nh, c.D, c.maxlen
-    Kp, Vp = R.poison(c, c.K0, c.V0, c.visible.any(1))
-    Kc, Vc = Kp.cuda(), Vp.cuda()
     store = torch.full((B, S, nh + 1, D), R.NAN, dtype=R.BF)     # q as a strided [B,nh,S,D] view of [B,S,nh+1,D]
     store[:, :, :nh] = c.q.transpose(1, 2)
     q = store.cuda()[:, :, :nh].transpose(1, 2)
@@ -131,8 +135,16 @@ def check_attn(lib, c):
     mask = mask.cuda()
     out = _nan(B, S, nh, D)
     _check(lib.ll_decode_attn_bf16(q.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), mask.data_ptr(), out.data_ptr(), B, nh, c.nkv, S, L, D, c.scale,
-                                   I3(q.stride(0), q.stride(1), q.stride(2)), I2(mask.stride(0), mask.stride(2)), _stream()), entry)
+                                   I3(q.stride(0), q.stride(1), q.stride(2)), I2(mask.stride(0), mask.stride(2)), _stream()), "ll_decode_attn_bf16")
     torch.cuda.synchronize()
+    return out
+
+
+def check_attn(lib, c):
+    entry = "ll_decode_attn_bf16"
+    Kp, Vp = R.poison(c, c.K0, c.V0, c.visible.any(1))
+    Kc, Vc = Kp.cuda(), Vp.cuda()
+    out = run_attn(lib, c, Kc, Vc)
     ref, absref = R.reference(c)
     _same_bits(entry, c, Kc, Kp, "key cache")
     _same_bits(entry, c, Vc, Vp, "value cache")
@@ -147,21 +159,39 @@ def test_decode_attn(lib, D, nh, nkv, S, maxlen, p0):
 
 
 # ------------------------------------------------------------------------------------------------------------------ ll_suffix_attn_rope_bf16
-def check_suffix(lib, c):
-    entry = "ll_suffix_attn_rope_bf16"
-    B, S, nh, D, L, rows = c.B, c.S, c.nh, c.D, c.maxlen, c.B * c.S
-    Kp, Vp = R.poison(c, c.K0, c.V0, c.old)
-    Kc, Vc = Kp.cuda(), Vp.cuda()
-    posid, freq, mask2d, qkv = c.position_ids.cuda(), c.inv_freq.cuda(), c.mask2d.cuda(), c.qkv.cuda()
+def run_prologue(lib, c):
+    """ll_suffix_prologue on the case's position ids and 2-D mask; returns cos, sin [B*S, D] and mask [B*S, maxlen] on the device"""
+    B, S, D, L, rows = c.B, c.S, c.D, c.maxlen, c.B * c.S
+    posid, freq, mask2d = c.position_ids.cuda(), c.inv_freq.cuda(), c.mask2d.cuda()
     pos = torch.tensor([c.pos], dtype=torch.long, device="cuda")
     cos, sin = _nan(rows, D), _nan(rows, D)
     mask = torch.ones(rows, L, dtype=torch.bool, device="cuda")
     _check(lib.ll_suffix_prologue(posid.data_ptr(), freq.data_ptr(), 1.0, mask2d.data_ptr(), c.mask2d_stride, pos.data_ptr(), cos.data_ptr(),
                                   sin.data_ptr(), mask.data_ptr(), B, S, D, L, _stream()), "ll_suffix_prologue")
-    out = _nan(rows, nh * D)
-    _check(lib.ll_suffix_attn_rope_bf16(qkv.data_ptr(), c.ld_qkv, cos.data_ptr(), sin.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), pos.data_ptr(),
-                                        mask.data_ptr(), out.data_ptr(), B, S, nh, c.nkv, L, D, c.scale, _stream()), entry)
     torch.cuda.synchronize()
+    return cos, sin, mask
+
+
+def run_suffix(lib, c, Kc, Vc, cos, sin, mask):
+    """one ll_suffix_attn_rope_bf16 call behind run_prologue; returns out [B*S, nh*D]"""
+    qkv = c.qkv.cuda()
+    pos = torch.tensor([c.pos], dtype=torch.long, device="cuda")
+    out = _nan(c.B * c.S, c.nh * c.D)
+    _check(lib.ll_suffix_attn_rope_bf16(qkv.data_ptr(), c.ld_qkv, cos.data_ptr(), sin.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), pos.data_ptr(),
+                                        mask.data_ptr(), out.data_ptr(), c.B, c.S, c.nh, c.nkv, c.maxlen, c.D, c.scale, _stream()),
+           "ll_suffix_attn_rope_bf16")
+    torch.cuda.synchronize()
+    return out
+
+
+def check_suffix(lib, c):
+    entry = "ll_suffix_attn_rope_bf16"
+    B, S, nh, D, L = c.B, c.S, c.nh, c.D, c.maxlen
+    Kp, Vp = R.poison(c, c.K0, c.V0, c.old)
+    Kc, Vc = Kp.cuda(), Vp.cuda()
+    posid, freq = c.position_ids.cuda(), c.inv_freq.cuda()
+    cos, sin, mask = run_prologue(lib, c)
+    out = run_suffix(lib, c, Kc, Vc, cos, sin, mask)
     # the reference from mask2d, *pos and position_ids alone: cos / sin with torch (the rotary module's own arithmetic on this device)
     cos_t, sin_t = R.rope_tables(freq, posid)
     inputs, written = R.suffix_expected(c, cos_t.cpu(), sin_t.cpu())
