@@ -23,7 +23,10 @@ int ll_gemm_bench(int M, int N, int K, int cfg, int splits, int out_f32, int ite
  * 2 = linear_launch onto the <= 64-row panel GEMM, 3 = linear_launch onto the LDS-DMA ring. */
 int ll_host_launch_probe(int kind, int n, float *us_per_launch);
 /* ll_linear_cfg : ll_linear (bf16 operands) through ONE kernel configuration of the tuning table (gemm.hip: g_pipe_cfgs), so that
- * every variant can be checked against a reference.  splits > 1: C receives `splits` raw f32 slabs (stride M * ldc). */
+ * every variant can be checked against a reference.  splits > 1: C receives `splits` raw f32 slabs (stride M * ldc).  What the launcher
+ * behind an entry cannot honour is refused (-1, nothing launched): M > 1 or splits > 1 on the GEMV entries 23..30, splits > 1 or
+ * K % 64 != 0 on the skinny entries 12..16, K % (64 * splits) != 0 on the ring and ping-pong tiles, K % (128 * splits) != 0 on the
+ * register-staged tiles 41..47, M > 64 or K != chunk * splits on the panel entries 31..33, lda / ldw off a multiple of 8. */
 int ll_linear_cfg(int cfg, const void *A, int lda, const void *W, int ldw, const float *bias, void *C, int ldc, int M, int N, int K,
                   int splits, int epi, int out_f32, void *stream);
 /* In-situ kernel timing of the GraphDiT launch chain: ll_dit_class_probe(handle, cls) makes the NEXT ll_dit_run in launch mode record a HIP
@@ -60,10 +63,28 @@ int ll_set_m64_packed(int on);
  * up to 128 rows, 64 beyond), 2 = up to 256 rows, 0 = the LDS-DMA ring; returns the previous value.  Takes effect at the next launch /
  * graph capture. */
 int ll_set_m128_panel(int on);
-/* ll_set_gemm_krot : the LDS-DMA GEMM sweeps its k-tiles starting at ((m_tile * (krot & 255) + n_tile * (krot >> 8 or 1)) mod
- * n_ktiles) instead of 0, so that workgroups sharing an operand tile do not miss L2 on the same lines at the same time.  0 = off.
- * Changes the f32 summation order per tile (deterministic).  Returns the previous setting. */
+/* ll_set_gemm_krot : the LDS-DMA GEMM sweeps its k-tiles starting at ((m_tile * krot + n_tile * (krot >> 8 or 1)) mod n_ktiles) -- the
+ * whole krot multiplies the M-tile index, its bits above the low eight (or 1 when they are zero) the N-tile index -- instead of 0, so
+ * that workgroups sharing an operand tile do not miss L2 on the same lines at the same time.  0 = off.  Changes the f32 summation order
+ * per tile (deterministic).  Returns the previous setting. */
 int ll_set_gemm_krot(int krot);
+/* ll_debug_last_gemm_path : the branch the dispatch behind ll_linear / ll_linear_splitk_bf16 / the two probes below took on this thread's
+ * last call.  Low byte: 0 none (refused), 1 GEMV, 2 <= 64-row panel, 3 multi-panel (65..256 rows), 4 rows16, 5 ring 32x32 (8 stages),
+ * 6 sixteen-wave 256x128, 7 sixteen-wave 128x128, 8 ring 64x64 on 2x2 waves, 9 ring 128x64, 10 unified-piece 64x64 on sixteen waves,
+ * 11 ring 64x64 on 4x2 waves, 12 ring 64x32, 13..16 the LL_GEMM_VARIANT=0 tiles 128x128 / 64x64 / 64x32 / 64x16, 17 f32.  Bits 8..15: K
+ * chunk / 128 of the panel kernels; bits 16..23: their 16-column tiles per workgroup (1, 2 or 4); bit 24: a pack_mfma16 copy was read. */
+int ll_debug_last_gemm_path(void);
+/* ll_linear_grouped2_probe : the two-row-group Linear of the GIN layer (rows [0, m_split) x W1 + bias1, rows [m_split, M) x W2 + bias2,
+ * m_split a multiple of 64; W2 = NULL: one group) on caller-provided operands.  splits > 1: `splits` raw f32 slabs (stride M * ldc). */
+int ll_linear_grouped2_probe(int dtype, const void *A, int lda, const void *W1, const void *W2, int ldw, const float *bias1,
+                             const float *bias2, void *C, int ldc, int M, int m_split, int N, int K, int splits, int epi, int out_f32,
+                             void *stream);
+/* ll_linear_packed_probe : ll_linear(LL_BF16) (splits > 1: raw f32 slabs, stride M * ldc) with `packed_scratch` (N * K bf16) registered
+ * as the pack_mfma16 copy of the dense weight W (ldw = K) for the duration of the call; the registry is left as it was found.  Not
+ * thread-safe: the entry is looked up, replaced and restored in three steps, so no other thread may register W or run a Linear on it
+ * meanwhile. */
+int ll_linear_packed_probe(const void *A, int lda, const void *W, int ldw, void *packed_scratch, const float *bias, void *C, int ldc,
+                           int M, int N, int K, int splits, int epi, int out_f32, void *stream);
 
 /* Launch-latency probe (tuning utility): average us per kernel over n launches of a trivial kernel
  * (kind 0 empty, 1 load+store, 2 dependent loads, 3 1-MB copy), eager stream (graph=0) or one hipGraph (graph=1). */

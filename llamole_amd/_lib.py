@@ -135,6 +135,9 @@ TUNING_SIGNATURES = {
     "ll_set_m128_panel": (_I, [_I]),
     "ll_set_m64_packed": (_I, [_I]),
     "ll_set_gemm_krot": (_I, [_I]),
+    "ll_debug_last_gemm_path": (_I, []),
+    "ll_linear_grouped2_probe": (_I, [_I, _P, _I, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "ll_linear_packed_probe": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ll_set_lnmod_multiwave": (_I, [_I]),
     "ll_set_stage_mod": (_I, [_I]),
     "ll_set_attn_waves": (_I, [_I]),

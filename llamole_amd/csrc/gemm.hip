@@ -26,6 +26,23 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 enum { EPI_NONE = 0, EPI_GELU = 1, EPI_SILU = 2, EPI_SOFTSIGN = 3 };
 
+// ll_debug_last_gemm_path (tuning build): which branch gemm_dispatch took on this thread's last call.  Low byte = the branch, bits 8..15 = NS
+// (K chunk / 128) of the panel kernels, bits 16..23 = their 16-column tiles per workgroup, bit 24 = a pack_mfma16 copy was read.
+enum {
+    PATH_NONE = 0, PATH_GEMV = 1, PATH_M64 = 2, PATH_M128 = 3, PATH_ROWS16 = 4, PATH_RING_32x32 = 5, PATH_W16_256x128 = 6,
+    PATH_W16_128x128 = 7, PATH_RING_64x64_2x2 = 8, PATH_RING_128x64 = 9, PATH_PIPEU_64x64 = 10, PATH_RING_64x64_4x2 = 11,
+    PATH_RING_64x32 = 12, PATH_V0_128x128 = 13, PATH_V0_64x64 = 14, PATH_V0_64x32 = 15, PATH_V0_64x16 = 16, PATH_F32 = 17,
+    PATH_PACKED = 1 << 24
+};
+#if LL_TUNING
+static thread_local int g_last_gemm_path = PATH_NONE;
+#define LL_PATH(p) (g_last_gemm_path = (p))
+#define LL_PATH_OR(p) (g_last_gemm_path |= (p))
+#else
+#define LL_PATH(p) ((void)0)
+#define LL_PATH_OR(p) ((void)0)
+#endif
+
 __device__ __forceinline__ float apply_epi(float v, int epi) {
     switch (epi) {
         case EPI_GELU: return gelu_erf(v);
@@ -72,7 +89,9 @@ __global__ __launch_bounds__(WM *WN * 64) void gemm_bf16_kernel(const bf16_t *__
             const int c = tid + it * NT;
             if (A_CH % NT == 0 || c < A_CH) {
                 const int row = c >> 3, ch = c & 7;
-                ra[it] = *reinterpret_cast<const uint4 *>(A + (int64_t)(m0 + row) * lda + k0 + ch * 8);
+                int ar = m0 + row;
+                ar = ar < M ? ar : M - 1;  // M edge: re-read a valid row (result discarded), so A needs no row padding
+                ra[it] = *reinterpret_cast<const uint4 *>(A + (int64_t)ar * lda + k0 + ch * 8);
             }
         }
 #pragma unroll
@@ -476,7 +495,11 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const bf16_t *__re
     const bf16_t *pa[MT];
     const bf16_t *pb[NTL];
 #pragma unroll
-    for (int i = 0; i < MT; ++i) pa[i] = A + (int64_t)(m0 + i * 16 + frow) * lda + fk * 8;
+    for (int i = 0; i < MT; ++i) {
+        int ar = m0 + i * 16 + frow;
+        ar = ar < M ? ar : M - 1;   // M edge: re-read a valid row (result discarded)
+        pa[i] = A + (int64_t)ar * lda + fk * 8;
+    }
 #pragma unroll
     for (int j = 0; j < NTL; ++j) {
         int gr = n0 + j * 16 + frow;
@@ -1080,6 +1103,7 @@ static int launch_m64_w(const bf16_t *A, int lda, const bf16_t *W, int ldw, void
     dim3 grid(cdiv(N, 16), 1, splits);
     const bf16_t *Wp = (N % 16 == 0 && ldw % 32 == 0) ? packed_copy_of(W) : nullptr;
     if (Wp) {
+        LL_PATH_OR(PATH_PACKED);
         if (out_f32)
             hipLaunchKernelGGL((gemm_m64_kernel<NS, WAVES, float, true>), grid, dim3(WAVES * 64), lds, s, A, lda, Wp, ldw, (float *)C, ldc, bias, M, N, slab_stride, epi);
         else
@@ -1116,7 +1140,7 @@ static int launch_m128(const bf16_t *A, int lda, const bf16_t *W, int ldw, void 
     const dim3 grid(cdiv(N, 16 * NT), cdiv(M, 64), splits);
     const bf16_t *Wp = (N % 16 == 0 && ldw % 32 == 0) ? packed_copy_of(W) : nullptr;
 #define LL_M128(T, P, WPTR) hipLaunchKernelGGL((gemm_m128_kernel<NS, NT, T, P>), grid, dim3(512), lds, s, A, lda, WPTR, ldw, (T *)C, ldc, bias, M, N, slab_stride, epi)
-    if (Wp) { if (out_f32) LL_M128(float, true, Wp); else LL_M128(bf16_t, true, Wp); }
+    if (Wp) { LL_PATH_OR(PATH_PACKED); if (out_f32) LL_M128(float, true, Wp); else LL_M128(bf16_t, true, Wp); }
     else { if (out_f32) LL_M128(float, false, W); else LL_M128(bf16_t, false, W); }
 #undef LL_M128
     return LL_OK;
@@ -1508,6 +1532,7 @@ void set_panel_gemm(bool on) { g_no_panel_gemm = on ? 0 : 1; }
 
 static int gemm_dispatch(int dtype, const void *A, int lda, const void *W, int ldw, const float *bias, void *C, int ldc,
                          int M, int N, int K, int splits, int64_t slab_stride, int epi, int out_f32, hipStream_t s) {
+    LL_PATH(PATH_NONE);
     LL_CHECK(M > 0 && N > 0 && K > 0, "ll_linear: empty problem M=%d N=%d K=%d", M, N, K);
     LL_CHECK(splits >= 1 && K % splits == 0, "ll_linear: K=%d not divisible by splits=%d", K, splits);
     const int kchunk = K / splits;
@@ -1521,7 +1546,10 @@ static int gemm_dispatch(int dtype, const void *A, int lda, const void *W, int l
             const char *ev = getenv("LL_GEMM_VARIANT");
             g_gemm_variant = ev ? atoi(ev) : 1;
         }
-        if (g_gemm_variant != 0 && M <= 4 && splits == 1 && K % 8 == 0) {
+        // the GEMV needs no variant: under LL_GEMM_VARIANT=0 it still takes the calls the guard above admits only for it (K % 64 != 0),
+        // which gemm_bf16_kernel's whole 64-wide k-tiles would cut short
+        if ((g_gemm_variant != 0 || kchunk % 64 != 0) && M <= 4 && splits == 1 && K % 8 == 0) {
+            LL_PATH(PATH_GEMV);
             switch (M) {
                 case 1: launch_gemv<1>(a, lda, w, ldw, C, ldc, bias, N, K, epi, out_f32, s); break;
                 case 2: launch_gemv<2>(a, lda, w, ldw, C, ldc, bias, N, K, epi, out_f32, s); break;
@@ -1538,6 +1566,7 @@ static int gemm_dispatch(int dtype, const void *A, int lda, const void *W, int l
             // hidden 768 -- q|k|v, fc1 and the output layer in one piece, fc2 as split-K slabs) run on eight waves like the others.  The odd
             // slice counts of hidden 1152 (1152 = 9 x 128, its proj slabs 3 x 128) only divide among FOUR waves, each then holds 36 panel
             // loads in flight, and that form measured slower than the LDS-DMA ring (1.53 vs 1.37 ms per step at batch 1, same box): not kept
+            LL_PATH(PATH_M64 | (kchunk / 128) << 8 | 1 << 16);
             switch (kchunk) {
                 case 1024: LL_TRY((launch_m64<8>(a, lda, w, ldw, C, ldc, bias, M, N, splits, slab_stride, epi, out_f32, s))); break;
                 case 768: LL_TRY((launch_m64<6>(a, lda, w, ldw, C, ldc, bias, M, N, splits, slab_stride, epi, out_f32, s))); break;
@@ -1557,6 +1586,7 @@ static int gemm_dispatch(int dtype, const void *A, int lda, const void *W, int l
         else if (kchunk == 512) LL_TRY((launch_m128<4, NT>(a, lda, w, ldw, C, ldc, bias, M, N, splits, slab_stride, epi, out_f32, s))); \
         else LL_TRY((launch_m128<2, NT>(a, lda, w, ldw, C, ldc, bias, M, N, splits, slab_stride, epi, out_f32, s)));              \
     } while (0)
+            LL_PATH(PATH_M128 | (kchunk / 128) << 8 | (M <= 128 ? 2 : 4) << 16);
             if (M <= 128) LL_PANELS(2); else LL_PANELS(4);
 #undef LL_PANELS
             LL_LAUNCH_CHECK();
@@ -1567,6 +1597,7 @@ static int gemm_dispatch(int dtype, const void *A, int lda, const void *W, int l
             // 5..16 rows (per-graph vectors of a GIN batch: virtual-node MLPs, projection head, decoder input; GraphDiT's hoisted
             // per-graph conditions): the weight-streaming MFMA Linear of the batched LLM decode (llm_rows16.hip) instead of 32x32 ring
             // tiles -- 13 -> ~5 us per launch on [16 x 2048 x 512] (profiles/r2_gin_kernel_stats.csv)
+            LL_PATH(PATH_ROWS16);
             LL_TRY(linear_rows16_launch(a, lda, w, ldw, bias, nullptr, 0.f, nullptr, 0, C, ldc, M, N, K, 0, out_f32, s));
             return LL_OK;
         }
@@ -1574,6 +1605,7 @@ static int gemm_dispatch(int dtype, const void *A, int lda, const void *W, int l
             // a few rows (several sequences decoding at once, one small graph): 32x32 tiles, 8-deep ring -- many small
             // workgroups and a small activation share of each one's ingest (tools/gemm_rows32_sweep.py: 13 vs 17 us on the
             // Qwen2-7B q|k|v shape, 55 vs 73 us on down_proj at 8-32 rows)
+            LL_PATH(PATH_RING_32x32);
             LL_TRY((launch_pipe<32, 32, 2, 2, 8>(a, lda, w, ldw, C, ldc, bias, M, N, K, splits, slab_stride, epi, out_f32, s)));
             LL_LAUNCH_CHECK();
             return LL_OK;
@@ -1584,11 +1616,13 @@ static int gemm_dispatch(int dtype, const void *A, int lda, const void *W, int l
             // fc1 at M = 2048 32.5 -> 22.6 us = 760 TF, hipBLASLt's MT256x128x64 kernel: 21.3 us; at M = 1024 17.8 -> 14.5 us)
             const long t256 = (long)cdiv(M, 256) * cdiv(N, 128) * splits, t128 = (long)cdiv(M, 128) * cdiv(N, 128) * splits;
             if (M >= 2048 && t256 >= 192) {
+                LL_PATH(PATH_W16_256x128);
                 LL_TRY((launch_pipe<256, 128, 4, 4, 3>(a, lda, w, ldw, C, ldc, bias, M, N, K, splits, slab_stride, epi, out_f32, s)));
                 LL_LAUNCH_CHECK();
                 return LL_OK;
             }
             if (t128 >= 192) {
+                LL_PATH(PATH_W16_128x128);
                 LL_TRY((launch_pipe<128, 128, 4, 4, 3>(a, lda, w, ldw, C, ldc, bias, M, N, K, splits, slab_stride, epi, out_f32, s)));
                 LL_LAUNCH_CHECK();
                 return LL_OK;
@@ -1599,20 +1633,26 @@ static int gemm_dispatch(int dtype, const void *A, int lda, const void *W, int l
             const long w12864 = (long)cdiv(M, 128) * cdiv(N, 64) * splits;
             const long w6464 = (long)cdiv(M, 64) * cdiv(N, 64) * splits;
             // 8-wave workgroups: more waves issuing LDS-DMA per CU lifts the per-CU ingest rate (~26 -> ~43 GB/s)
-            if (M <= 64 && cdiv(N, 64) * splits >= 256)
+            if (M <= 64 && cdiv(N, 64) * splits >= 256) {
                 // pure weight streaming (e.g. the 180 k-template head, 740 MB): 4-wave 64x64 tiles, ~3 workgroups per CU
                 // in flight, measured 4.8-5.3 TB/s (60-66 % of the 8 TB/s HBM peak)
+                LL_PATH(PATH_RING_64x64_2x2);
                 LL_TRY((launch_pipe<64, 64, 2, 2, 4>(a, lda, w, ldw, C, ldc, bias, M, N, K, splits, slab_stride, epi, out_f32, s)));
-            else if (w12864 >= 1024)
+            } else if (w12864 >= 1024) {
+                LL_PATH(PATH_RING_128x64);
                 LL_TRY((launch_pipe<128, 64, 4, 2, 4>(a, lda, w, ldw, C, ldc, bias, M, N, K, splits, slab_stride, epi, out_f32, s)));
-            else if (w6464 >= 200 && M > 64)
+            } else if (w6464 >= 200 && M > 64) {
                 // sixteen waves per 64 x 64 tile, one DMA piece per wave (round 2: 5-8 % faster than eight waves with two pieces each
                 // on the GraphDiT block shapes at M = 128..512, profiles/r2_gemm_16w64_sweep_m512.txt)
+                LL_PATH(PATH_PIPEU_64x64);
                 LL_TRY((launch_pipeu<64, 64, 4, 4, 4>(a, lda, w, ldw, C, ldc, bias, M, N, K, splits, slab_stride, epi, out_f32, s)));
-            else if (w6464 >= 200 || (N % 32 != 0 && N < 64))
+            } else if (w6464 >= 200 || (N % 32 != 0 && N < 64)) {
+                LL_PATH(PATH_RING_64x64_4x2);
                 LL_TRY((launch_pipe<64, 64, 4, 2, 4>(a, lda, w, ldw, C, ldc, bias, M, N, K, splits, slab_stride, epi, out_f32, s)));
-            else
+            } else {
+                LL_PATH(PATH_RING_64x32);
                 LL_TRY((launch_pipe<64, 32, 4, 1, 4>(a, lda, w, ldw, C, ldc, bias, M, N, K, splits, slab_stride, epi, out_f32, s)));
+            }
             LL_LAUNCH_CHECK();
             return LL_OK;
         }
@@ -1620,18 +1660,24 @@ static int gemm_dispatch(int dtype, const void *A, int lda, const void *W, int l
         const long wg128 = (long)cdiv(M, 128) * cdiv(N, 128) * splits;
         const long wg64 = (long)cdiv(M, 64) * cdiv(N, 64) * splits;
         const long wg6432 = (long)cdiv(M, 64) * cdiv(N, 32) * splits;
-        if (wg128 >= 512)
+        if (wg128 >= 512) {
+            LL_PATH(PATH_V0_128x128);
             launch_bf16<128, 128, 2, 2>(a, lda, w, ldw, C, ldc, bias, M, N, K, splits, slab_stride, epi, out_f32, s);
-        else if (wg64 >= 256 || (M > 64 && wg6432 < 256))
+        } else if (wg64 >= 256 || (M > 64 && wg6432 < 256)) {
+            LL_PATH(PATH_V0_64x64);
             launch_bf16<64, 64, 2, 2>(a, lda, w, ldw, C, ldc, bias, M, N, K, splits, slab_stride, epi, out_f32, s);
-        else if (wg6432 >= 256 || N % 16 != 0)
+        } else if (wg6432 >= 256 || N % 16 != 0) {
+            LL_PATH(PATH_V0_64x32);
             launch_bf16<64, 32, 4, 1>(a, lda, w, ldw, C, ldc, bias, M, N, K, splits, slab_stride, epi, out_f32, s);
-        else
+        } else {
+            LL_PATH(PATH_V0_64x16);
             launch_bf16<64, 16, 4, 1>(a, lda, w, ldw, C, ldc, bias, M, N, K, splits, slab_stride, epi, out_f32, s);
+        }
     } else if (dtype == LL_F32) {
         LL_CHECK(kchunk % 16 == 0, "ll_linear(f32): K per split (%d) must be a multiple of 16", kchunk);
         LL_CHECK(lda % 4 == 0 && ldw % 4 == 0, "ll_linear(f32): lda/ldw must be multiples of 4 elements");
         dim3 grid(cdiv(N, 64), cdiv(M, 64), splits);
+        LL_PATH(PATH_F32);
         // out_f32 is implied (operand dtype is f32)
         hipLaunchKernelGGL((gemm_f32_kernel<float>), grid, dim3(256), 0, s, (const float *)A, lda, (const float *)W,
                            ldw, (float *)C, ldc, bias, M, N, kchunk, slab_stride, epi);
@@ -1850,7 +1896,18 @@ extern "C" int ll_linear_cfg(int cfg, const void *A, int lda, const void *W, int
     using namespace ll;
     const int ncfg = (int)(sizeof(g_pipe_cfgs) / sizeof(g_pipe_cfgs[0]));
     LL_CHECK(cfg >= 0 && cfg < ncfg, "cfg %d out of range [0,%d)", cfg, ncfg);
-    LL_CHECK(A && W && C && splits >= 1 && K % splits == 0, "bad argument");
+    LL_CHECK(A && W && C && M > 0 && N > 0 && K > 0 && splits >= 1 && K % splits == 0, "bad argument");
+    LL_CHECK(lda % 8 == 0 && ldw % 8 == 0, "ll_linear_cfg: lda/ldw must be multiples of 8 elements");
+    // what the launcher behind a table entry cannot honour is refused, not ignored (the `stages` column names the kernel family)
+    const int fam = g_pipe_cfgs[cfg].stages / 100;
+    if (fam == 2)        // gemv_bf16_kernel<1, R, UNR>: one row, the whole K, 16-byte steps
+        LL_CHECK(M == 1 && splits == 1 && K % 8 == 0, "ll_linear_cfg: cfg %d is a GEMV: M = 1, splits = 1, K %% 8 == 0 (M=%d splits=%d K=%d)", cfg, M, splits, K);
+    else if (fam == 1)   // gemm_skinny_kernel: K is split over the waves inside the workgroup, whole 64-wide k-tiles
+        LL_CHECK(splits == 1 && K % 64 == 0, "ll_linear_cfg: cfg %d (skinny) takes splits = 1 and K %% 64 == 0 (splits=%d K=%d)", cfg, splits, K);
+    else if (fam == 4)   // gemm_rs_kernel: nk = kchunk / 128 whole k-tiles
+        LL_CHECK(K % (128 * splits) == 0, "ll_linear_cfg: cfg %d (BK = 128) needs K %% (128 * splits) == 0 (K=%d splits=%d)", cfg, K, splits);
+    else if (fam != 3)   // LDS-DMA ring and ping-pong tiles: nk = kchunk / 64 whole k-tiles (the panel entries check K = NS * 128 * splits themselves)
+        LL_CHECK(K % (64 * splits) == 0, "ll_linear_cfg: cfg %d needs K %% (64 * splits) == 0 (K=%d splits=%d)", cfg, K, splits);
     LL_TRY(g_pipe_cfgs[cfg].fn((const bf16_t *)A, lda, (const bf16_t *)W, ldw, C, ldc, bias, M, N, K, splits, (int64_t)M * ldc, epi,
                                splits > 1 ? 1 : out_f32, (hipStream_t)stream));
     LL_LAUNCH_CHECK();
@@ -2043,6 +2100,42 @@ extern "C" int ll_linear_splitk_bf16(const void *A, int lda, const void *W, int 
 }
 
 #if LL_TUNING
+extern "C" int ll_debug_last_gemm_path(void) { return ll::g_last_gemm_path; }
+
+// linear_grouped2_launch as the GIN layer calls it; splits > 1: `splits` raw f32 slabs of M x ldc
+extern "C" int ll_linear_grouped2_probe(int dtype, const void *A, int lda, const void *W1, const void *W2, int ldw, const float *bias1,
+                                        const float *bias2, void *C, int ldc, int M, int m_split, int N, int K, int splits, int epi,
+                                        int out_f32, void *stream) {
+    using namespace ll;
+    LL_CHECK(A && W1 && C, "ll_linear_grouped2_probe: null argument");
+    LL_PATH(PATH_NONE);
+    return linear_grouped2_launch(dtype, A, lda, W1, W2, ldw, bias1, bias2, C, ldc, M, m_split, N, K, splits, (int64_t)M * ldc, epi, out_f32,
+                                  (hipStream_t)stream);
+}
+
+// ll_linear / split-K slabs (stride M * ldc) on bf16 operands with W registered as having the pack_mfma16 copy `packed_scratch` (N * K
+// elements, written here when N % 16 == 0 and K % 32 == 0; ldw must be K, as for every registered weight).  The registry is left as found.
+extern "C" int ll_linear_packed_probe(const void *A, int lda, const void *W, int ldw, void *packed_scratch, const float *bias, void *C,
+                                      int ldc, int M, int N, int K, int splits, int epi, int out_f32, void *stream) {
+    using namespace ll;
+    LL_CHECK(A && W && C && packed_scratch && splits >= 1, "ll_linear_packed_probe: bad argument");
+    LL_CHECK(ldw == K, "ll_linear_packed_probe: a packed copy stands for a dense weight (ldw=%d, K=%d)", ldw, K);
+    hipStream_t st = (hipStream_t)stream;
+    if (N > 0 && N % 16 == 0 && K % 32 == 0) LL_TRY(pack_mfma16((const bf16_t *)W, (bf16_t *)packed_scratch, N, K, st));
+    const void *before = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_packed_mu);
+        auto it = g_packed.find(W);
+        if (it != g_packed.end()) before = it->second;
+    }
+    register_packed_weight(W, packed_scratch);
+    const bool raw = splits > 1;
+    const int rc = gemm_dispatch(LL_BF16, A, lda, W, ldw, raw ? nullptr : bias, C, ldc, M, N, K, splits, (int64_t)M * ldc,
+                                 raw ? (int)EPI_NONE : epi, raw ? 1 : out_f32, st);
+    register_packed_weight(W, before);
+    return rc;
+}
+
 extern "C" int ll_set_gemm_krot(int krot) {
     const int old = ll::g_gemm_krot;
     ll::g_gemm_krot = krot < 0 ? 0 : krot;

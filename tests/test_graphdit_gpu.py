@@ -58,75 +58,102 @@ def case(request):
     return dict(name=name, g=g, m=m, cfg=cfg, meta=meta, sd=sd, B=B, seed=seed, props=props, text=text, n_nodes=n_nodes)
 
 
+def _gemm_operands(M, N, K, seed, f32=False):
+    """A [M,K], W [N,K] / sqrt K, bias [N] on the device, with their float64 reference (tests/gemm_reference.py: lin, e)"""
+    from tests import gemm_reference as G
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    A = torch.randn(M, K, device="cuda", generator=g)
+    W = torch.randn(N, K, device="cuda", generator=g) / K ** 0.5
+    bias = torch.randn(N, device="cuda", generator=g)
+    if not f32:
+        A, W = A.bfloat16(), W.bfloat16()
+    return A, W, bias, {b: G.linear64_on(A, W, bias if b else None, f32) for b in (False, True)}
+
+
+def _check_slabs(G, R, what, slabs, A, W, lin, e):
+    """raw split-K slabs [splits, M, N] f32: each against the float64 sum over its own K range, their sum against the whole"""
+    splits, K = slabs.shape[0], A.shape[1]
+    kc = K // splits
+    for z in range(splits):
+        lin_z, e_z = G.linear64_on(A[:, z * kc:(z + 1) * kc], W[:, z * kc:(z + 1) * kc], None)
+        outside, pos = R.check(slabs[z], *G.interval(lin_z, e_z, G.NONE, 1))
+        assert outside == 0, (what, f"slab {z}: {outside} elements outside their interval, largest position {pos}")
+    outside, pos = G.check_sum(slabs.double().sum(0), lin, e)
+    assert outside == 0, (what, f"slab sum: {outside} elements outside lin +- e, largest position {pos}")
+
+
 def test_linear_matches_torch():
-    import ctypes as C
+    """ll_linear on the GraphDiT / decode shapes, f32 and bf16 operands, bias + GELU: every element inside the rounding interval of the
+    float64 reference (tests/gemm_reference.py; the small shapes of every dispatch branch are in tests/test_gemm_reference_gpu.py)"""
     from llamole_amd import _lib
+    from tests import gemm_reference as G
+    from tests import linear_reference as R
     lib = _lib.load()
-    torch.manual_seed(0)
-    for (M, N, K) in [(64, 176, 128), (512, 3072, 1024), (450, 266, 256), (3, 128, 768), (1024, 4096, 1024), (64, 1024, 4096),
-                      (1, 3584, 3584), (2, 515, 1032), (4, 18944, 3584), (17, 192, 64),
-                      # batch >= 16: sixteen-wave 128x128 / 256x128 tiles, ragged edges
-                      (2048, 3072, 1024), (2100, 3000, 256), (1024, 1024, 4096), (1500, 2050, 512),
-                      # M <= 64 all-in-flight kernel (gemm_m64_kernel): K chunks of 1024 / 512 / 256, ragged M and N
-                      (64, 3072, 1024), (40, 4096, 1024), (64, 1024, 512), (33, 784, 256), (5, 1000, 1024),
-                      # 65..128 rows: two 64-row panels (gemm_m128_kernel), K chunks 1024 / 512 / 256, ragged M and N (odd tile counts)
-                      (128, 3072, 1024), (100, 4096, 1024), (65, 1024, 512), (127, 784, 256), (100, 176, 1024), (128, 1040, 512),
-                      (256, 3072, 1024), (192, 4096, 1024), (130, 1000, 512), (256, 176, 256),
-                      # 5..32 rows over large weight matrices (several sequences decoding at once), ragged N
-                      (8, 18944, 3584), (16, 3584, 18944), (23, 4611, 3584), (32, 2048, 2112)]:
-        lib.ll_set_m128_panel(2 if M == 256 else 1)      # 225..256 rows on the 64-column form of the panel kernel: opt-in
-        Mp = (M + 127) // 128 * 128
-        A = torch.zeros(Mp, K, device="cuda")
-        A[:M] = torch.randn(M, K, device="cuda")
-        W = torch.randn(N, K, device="cuda") / K ** 0.5
-        bias = torch.randn(N, device="cuda")
-        ref = torch.nn.functional.gelu(A[:M].double() @ W.double().t() + bias.double()).float()
-        out = torch.empty(M, N, device="cuda")
-        if K % 16 == 0:
-            _lib.check(lib.ll_linear(0, _lib.dptr(A), K, _lib.dptr(W), K, _lib.dptr(bias), _lib.dptr(out), N, M, N, K, 1, 1, None))
-            torch.cuda.synchronize()
-            assert torch.allclose(out, ref, rtol=1e-4, atol=1e-4), (M, N, K, (out - ref).abs().max())
-        Ab, Wb = A[:M].bfloat16().contiguous(), W.bfloat16().contiguous()      # exact M rows: bf16 path needs no padding
-        refb = torch.nn.functional.gelu(Ab.double() @ Wb.double().t() + bias.double()).float()
-        outb = torch.empty(M, N, device="cuda")
-        _lib.check(lib.ll_linear(1, _lib.dptr(Ab), K, _lib.dptr(Wb), K, _lib.dptr(bias), _lib.dptr(outb), N, M, N, K, 1, 1, None))
-        torch.cuda.synchronize()
-        assert torch.allclose(outb, refb, rtol=2e-3, atol=2e-3), (M, N, K, (outb - refb).abs().max())
-        outh = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
-        _lib.check(lib.ll_linear(1, _lib.dptr(Ab), K, _lib.dptr(Wb), K, _lib.dptr(bias), _lib.dptr(outh), N, M, N, K, 1, 0, None))
-        torch.cuda.synchronize()
-        assert torch.allclose(outh.float(), refb, rtol=2e-2, atol=2e-2)
-    lib.ll_set_m128_panel(1)
+    shapes = [(64, 176, 128), (512, 3072, 1024), (450, 266, 256), (3, 128, 768), (1024, 4096, 1024), (64, 1024, 4096),
+              (1, 3584, 3584), (2, 515, 1032), (4, 18944, 3584), (17, 192, 64),
+              # batch >= 16: sixteen-wave 128x128 / 256x128 tiles, ragged edges
+              (2048, 3072, 1024), (2100, 3000, 256), (1024, 1024, 4096), (1500, 2050, 512),
+              # M <= 64 all-in-flight kernel (gemm_m64_kernel): K chunks of 1024 / 512 / 256, ragged M and N
+              (64, 3072, 1024), (40, 4096, 1024), (64, 1024, 512), (33, 784, 256), (5, 1000, 1024),
+              # 65..128 rows: two 64-row panels (gemm_m128_kernel), K chunks 1024 / 512 / 256, ragged M and N (odd tile counts)
+              (128, 3072, 1024), (100, 4096, 1024), (65, 1024, 512), (127, 784, 256), (100, 176, 1024), (128, 1040, 512),
+              (256, 3072, 1024), (192, 4096, 1024), (130, 1000, 512), (256, 176, 256),
+              # 5..32 rows over large weight matrices (several sequences decoding at once), ragged N
+              (8, 18944, 3584), (16, 3584, 18944), (23, 4611, 3584), (32, 2048, 2112)]
+    try:
+        for i, (M, N, K) in enumerate(shapes):
+            lib.ll_set_m128_panel(2 if M == 256 else 1)      # 225..256 rows on the 64-column form of the panel kernel: opt-in
+            if K % 16 == 0:
+                A, W, bias, ref = _gemm_operands(M, N, K, i, f32=True)
+                Ap = torch.full(((M + 63) // 64 * 64, K), float("nan"), device="cuda")      # readable for round_up(M, 64) rows, not zero
+                Ap[:M] = A
+                out = torch.empty(M, N, device="cuda")
+                _lib.check(lib.ll_linear(0, _lib.dptr(Ap), K, _lib.dptr(W), K, _lib.dptr(bias), _lib.dptr(out), N, M, N, K, 1, 1, None))
+                outside, pos = R.check(out, *G.interval(*ref[True], G.GELU, 1))
+                assert outside == 0, ("f32", M, N, K, outside, pos)
+                want = G.gelu64(ref[True][0]).float()       # the interval is a worst case over K: the flat tolerance stays beside it
+                assert torch.allclose(out, want, rtol=1e-4, atol=1e-4), (M, N, K, (out - want).abs().max())
+            Ab, Wb, bias, ref = _gemm_operands(M, N, K, i)      # exact M rows: the bf16 path needs no padding
+            for out_f32 in (1, 0):
+                outb = torch.empty(M, N, device="cuda", dtype=torch.float32 if out_f32 else torch.bfloat16)
+                _lib.check(lib.ll_linear(1, _lib.dptr(Ab), K, _lib.dptr(Wb), K, _lib.dptr(bias), _lib.dptr(outb), N, M, N, K, 1, out_f32, None))
+                outside, pos = R.check(outb, *G.interval(*ref[True], G.GELU, out_f32))
+                assert outside == 0, ("bf16", M, N, K, out_f32, outside, pos)
+                tol = 2e-3 if out_f32 else 2e-2
+                assert torch.allclose(outb.float(), G.gelu64(ref[True][0]).float(), rtol=tol, atol=tol), (M, N, K, out_f32)
+    finally:
+        lib.ll_set_m128_panel(1)
 
 
 def test_register_staged_gemm_configs_match_torch():
-    """gemm_rs_kernel (tuning-table ids 41..47) and gemm_pp_kernel (48..55) through ll_linear_cfg: ragged M and N, split-K slabs,
-    bias + GELU epilogue, K chunks down to 2 k-tiles (shorter than the ring)."""
+    """gemm_rs_kernel (tuning-table ids 41..47), gemm_pp_kernel (48..55) and the later ring entries through ll_linear_cfg at the GraphDiT
+    shapes: ragged M and N, split-K slabs, bias + GELU epilogue, K chunks down to 2 k-tiles (shorter than the ring); every element inside
+    the rounding interval of the float64 reference (every entry at its tile edges: tests/test_gemm_reference_gpu.py)"""
     from llamole_amd import _lib
+    from tests import gemm_reference as G
+    from tests import linear_reference as R
     lib = _lib.load()
-    torch.manual_seed(2)
-    for cfg in (41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51, 52, 53, 54, 55, 56, 57, 58, 60, 61, 62, 63, 64, 65, 66, 67):
-        for (M, N, K, splits) in [(512, 4096, 1024, 1), (512, 1024, 4096, 4), (200, 1000, 256, 1), (130, 72, 128, 1), (2048, 3072, 1024, 1),
-                                  (64, 176, 1024, 2)]:
-            A = torch.randn(M, K, device="cuda").bfloat16()
-            W = (torch.randn(N, K, device="cuda") / K ** 0.5).bfloat16()
-            bias = torch.randn(N, device="cuda")
-            lin = A.double() @ W.double().t()
+    for i, (M, N, K, splits) in enumerate([(512, 4096, 1024, 1), (512, 1024, 4096, 4), (200, 1000, 256, 1), (130, 72, 128, 1),
+                                           (2048, 3072, 1024, 1), (64, 176, 1024, 2)]):
+        A, W, bias, ref = _gemm_operands(M, N, K, 100 + i)
+        gelu, plain = G.interval(*ref[True], G.GELU, 1), G.interval(*ref[False], G.NONE, 0)
+        for cfg in (41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51, 52, 53, 54, 55, 56, 57, 58, 60, 61, 62, 63, 64, 65, 66, 67):
             if splits == 1:
                 out = torch.empty(M, N, device="cuda")
                 _lib.check(lib.ll_linear_cfg(cfg, _lib.dptr(A), K, _lib.dptr(W), K, _lib.dptr(bias), _lib.dptr(out), N, M, N, K, 1, 1, 1, None))
-                torch.cuda.synchronize()
-                ref = torch.nn.functional.gelu(lin + bias.double()).float()
-                assert torch.allclose(out, ref, rtol=2e-3, atol=2e-3), (cfg, M, N, K, (out - ref).abs().max())
+                outside, pos = R.check(out, *gelu)
+                assert outside == 0, (cfg, M, N, K, outside, pos)
+                assert torch.allclose(out, gelu[2], rtol=2e-3, atol=2e-3), (cfg, M, N, K, (out - gelu[2]).abs().max())
                 outh = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
                 _lib.check(lib.ll_linear_cfg(cfg, _lib.dptr(A), K, _lib.dptr(W), K, None, _lib.dptr(outh), N, M, N, K, 1, 0, 0, None))
-                torch.cuda.synchronize()
-                assert torch.allclose(outh.float(), lin.float(), rtol=2e-2, atol=2e-2), (cfg, M, N, K)
+                outside, pos = R.check(outh, *plain)
+                assert outside == 0, (cfg, M, N, K, "bf16", outside, pos)
+                assert torch.allclose(outh.float(), ref[False][0].float(), rtol=2e-2, atol=2e-2), (cfg, M, N, K)
             else:
                 slabs = torch.empty(splits, M, N, device="cuda")
                 _lib.check(lib.ll_linear_cfg(cfg, _lib.dptr(A), K, _lib.dptr(W), K, None, _lib.dptr(slabs), N, M, N, K, splits, 0, 1, None))
-                torch.cuda.synchronize()
-                assert torch.allclose(slabs.sum(0), lin.float(), rtol=2e-3, atol=2e-3), (cfg, M, N, K, splits)
+                _check_slabs(G, R, (cfg, M, N, K, splits), slabs, A, W, *ref[False])
+                assert torch.allclose(slabs.sum(0), ref[False][0].float(), rtol=2e-3, atol=2e-3), (cfg, M, N, K, splits)
 
 
 def test_conditioning_vectors(case):
@@ -313,22 +340,25 @@ def test_training_forward_matches_oracle_and_reference(name):
 
 
 def test_linear_splitk_matches_torch():
-    """ll_linear_splitk_bf16 (few rows x short, wide weight matrix: batch-8/16 decode through down_proj) vs f64 PyTorch."""
+    """ll_linear_splitk_bf16 (few rows x short, wide weight matrix: batch-8/16 decode through down_proj) at the decode shapes: every raw
+    slab of the workspace, their sum and the bf16 result (bias + SiLU) inside the rounding intervals of the float64 reference"""
     from llamole_amd import _lib
+    from tests import gemm_reference as G
+    from tests import linear_reference as R
     lib = _lib.load()
-    torch.manual_seed(1)
-    for (M, N, K, splits) in [(8, 3584, 18944, 4), (16, 1000, 8192, 2), (5, 96, 1024, 16), (32, 3584, 18944, 4),
-                              (100, 1024, 4096, 4), (128, 1024, 1024, 4), (64, 1024, 4096, 4)]:       # panel kernels with K slabs
-        A = torch.randn(M, K, device="cuda").bfloat16()
-        W = (torch.randn(N, K, device="cuda") / K ** 0.5).bfloat16()
-        bias = torch.randn(N, device="cuda")
+    for i, (M, N, K, splits) in enumerate([(8, 3584, 18944, 4), (16, 1000, 8192, 2), (5, 96, 1024, 16), (32, 3584, 18944, 4),
+                                           (100, 1024, 4096, 4), (128, 1024, 1024, 4), (64, 1024, 4096, 4)]):       # panel kernels with K slabs
+        A, W, bias, ref = _gemm_operands(M, N, K, 200 + i)
         ws = torch.empty(splits * M * N, device="cuda")
         out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
         _lib.check(lib.ll_linear_splitk_bf16(_lib.dptr(A), K, _lib.dptr(W), K, _lib.dptr(bias), _lib.dptr(out), N, M, N, K, 2, splits,
                                              _lib.dptr(ws), None))
-        torch.cuda.synchronize()
-        ref = torch.nn.functional.silu(A.double() @ W.double().t() + bias.double()).float()
-        assert torch.allclose(out.float(), ref, rtol=2e-2, atol=2e-2), (M, N, K, (out.float() - ref).abs().max())
+        _check_slabs(G, R, (M, N, K, splits), ws.view(splits, M, N), A, W, *ref[False])
+        silu = G.interval(*ref[True], G.SILU, 0)
+        outside, pos = R.check(out, *silu)
+        assert outside == 0, (M, N, K, splits, outside, pos)
+        want = G.epi64(ref[True][0], G.SILU).float()
+        assert torch.allclose(out.float(), want, rtol=2e-2, atol=2e-2), (M, N, K, (out.float() - want).abs().max())
     assert lib.ll_linear_splitk_bf16(_lib.dptr(A), K, _lib.dptr(W), K, None, _lib.dptr(out), N, M, N, K, 0, 1, _lib.dptr(ws), None) == -1
 
 
