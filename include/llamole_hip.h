@@ -327,6 +327,36 @@ int ll_suffix_attn_rope_split_bf16(const void *qkv, int64_t ld_qkv, const void *
                                    const void *mask, void *out, int B, int S, int nh, int nkv, int maxlen, int D, float scale,
                                    const void *q_norm_w, const void *k_norm_w, float eps, void *workspace, int64_t workspace_bytes,
                                    void *stream);
+/* ---- the microscaled FP8 (OCP MXFP8) KV cache: a static cache of D + D/32 bytes per row instead of 2 D ------------------------------------
+ * Storage, per cache layer four contiguous uint8 tensors: K codes and V codes [B,nkv,maxlen,D] (FP8 E4M3, OCP e4m3fn) and K scales and
+ *     V scales [B,nkv,maxlen,D/32] (E8M0: the byte e + 127 of the scale 2^e shared by 32 consecutive elements of head_dim).  The stored row of a
+ *     slot is the MX rounding (the quantiser of ll_wq_quantize_bf16 at 8 bits, bit for bit: amax of the block on the bf16 values, the smallest
+ *     e with amax * 2^-e <= 448 clamped to [-117, 119], elements rounded to nearest, ties to even) of the bf16 row that the bf16 entry points
+ *     above store: K behind the optional head RMSNorm and the rotation, V as it leaves q|k|v.  code * 2^e is exactly a bf16 number.
+ *     D in {64,128}; the code tensors 8-byte aligned.
+ * ll_kv8_store_bf16 : ll_kv_append_bf16 for such a cache: quantise the S rows of k_new / v_new [B,nkv,S,D] (element strides of dims 0..2,
+ *     any S >= 1) into slots *pos .. *pos+S-1; rows past the last slot are dropped.
+ * ll_kv8_load_bf16  : dequantise slots [0, min(maxlen, *pos + extra)) of a layer into bf16 K / V [B,nkv,maxlen,D] (16-byte aligned; the other
+ *     slots are left as they are); *pos is read on the device, extra >= 0.  Exact.
+ * ll_decode_attn_rope_kv8 / ll_suffix_attn_rope_kv8 : ll_decode_attn_rope_split_bf16 / ll_suffix_attn_rope_split_bf16 on such a cache, for
+ *     every maxlen in 1..131072: the same arguments with the four cache tensors in place of Kc / Vc, the same two launches (partial per range
+ *     of 512 keys, combine), the same workspace (ll_attn_split_workspace_bytes), bounds, masking rules and fixed summation orders; LL_EINVAL
+ *     beyond the bounds, nothing launched.  Codes are expanded to f32 exactly; dots and sums are f32.  The new rows are rotated, rounded to
+ *     bf16 and quantised by the workgroups whose range holds them, which attend to the DEQUANTISED row -- the result is attention over what
+ *     the cache holds, at this step as at every later one; the codes and scale bytes of a slot are stored by exactly one workgroup and are
+ *     bit for bit the MX rounding of the row ll_decode_attn_rope_split_bf16 stores from the same inputs.  Masked slots may hold anything (the
+ *     NaN code 0x7f, the scale byte 0xff). */
+int ll_kv8_store_bf16(void *Kq, void *Ks, void *Vq, void *Vs, const void *k_new, const void *v_new, const int64_t *pos, int B, int nkv, int S,
+                      int maxlen, int D, const int64_t *kstr, const int64_t *vstr, void *stream);
+int ll_kv8_load_bf16(const void *Kq, const void *Ks, const void *Vq, const void *Vs, void *K, void *V, const int64_t *pos, int extra, int B,
+                     int nkv, int maxlen, int D, void *stream);
+int ll_decode_attn_rope_kv8(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, int64_t cs_stride, void *Kq, void *Ks, void *Vq,
+                            void *Vs, const int64_t *pos, const void *mask, int64_t mask_stride, void *out, int B, int nh, int nkv, int maxlen,
+                            int D, float scale, const void *q_norm_w, const void *k_norm_w, float eps, void *workspace,
+                            int64_t workspace_bytes, void *stream);
+int ll_suffix_attn_rope_kv8(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, void *Kq, void *Ks, void *Vq, void *Vs,
+                            const int64_t *pos, const void *mask, void *out, int B, int S, int nh, int nkv, int maxlen, int D, float scale,
+                            const void *q_norm_w, const void *k_norm_w, float eps, void *workspace, int64_t workspace_bytes, void *stream);
 /* ll_decode_prologue_dyn / ll_suffix_prologue_dyn : the two prologues for dynamic NTK rope (transformers dynamic_rope_update) without its
  *     host read of the position ids.  With L = max(position_ids of the call) + 1, read on the device by every workgroup, the frequencies are
  *     inv_freq0 [D/2] (the module's constructed original_inv_freq) while L <= max_pos (= config.max_position_embeddings) and row

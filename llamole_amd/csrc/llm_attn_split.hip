@@ -5,7 +5,7 @@
 //       heads that share a KV head (GT = nh / nkv for groups of 2 / 4 / 7, else 1: a K / V row is fetched once per group) and per query row
 //       r = b*S + s.  It writes the running maximum m, the sum of exponentials l and the un-normalised f32 output of its range to the
 //       workspace.  A range without a visible key writes (m, l) = (-inf, 0) after reading its 512 mask bytes and nothing else.
-//   attn_split_combine_kernel  grid (nh, rows): out = sum_r exp(m_r - M) acc_r / sum_r exp(m_r - M) l_r, rounded once to bf16; ranges with
+//   attn_split_combine_kernel  (attn_split.h) grid (nh, rows): out = sum_r exp(m_r - M) acc_r / sum_r exp(m_r - M) l_r, rounded once to bf16; ranges with
 //       m_r = -inf are skipped (their weight is 0 by a select, not by exp(-inf - -inf)), a row without any visible key gives zeros.
 // Access pattern and lane roles are attn_decode.h's (a wave-level load covers RPI whole rows, 16 B per lane, DPP row sums), with all 16 (D = 128)
 // or 8 (D = 64) key loads of a lane's share of the range in flight before the rotary arithmetic and its value loads in flight under the softmax
@@ -18,17 +18,10 @@
 // range holds the slot.
 #include "common.h"
 #include "attn_decode.h"
+#include "attn_split.h"
 #include "head_pair.h"
 
 namespace ll {
-
-constexpr int SPLIT_RANGE = 512;                                    // keys per workgroup = one mask byte per thread, two tiles of 256 keys
-constexpr int SPLIT_TILES = SPLIT_RANGE / 256;
-constexpr int SPLIT_MAXLEN = 131072;
-constexpr int SPLIT_MAX_RANGES = SPLIT_MAXLEN / SPLIT_RANGE;       // 256
-constexpr int SPLIT_MAX_S = 16;
-constexpr int COMBINE_THREADS = 512;
-static_assert(SPLIT_RANGE == ATTN_THREADS, "one mask byte and one score per thread");
 
 // qkv rows r (stride ld_qkv), cos / sin rows r (stride cs0: 0 broadcasts), mask rows r (stride ms0), r = b*S + s; query row s sits at slot *pos + s.
 // ml [rows][nh][nr][2] f32 (m, l), acc [rows][nh][nr][D] f32.
@@ -224,66 +217,6 @@ __global__ __launch_bounds__(ATTN_THREADS) void attn_split_partial_kernel(const 
         for (int w = 0; w < ATTN_WAVES; ++w) o += part[(g * ATTN_WAVES + w) * D + d];
         accw[(wbase + (int64_t)g * nr) * D + d] = o;
     }
-}
-
-// grid (nh, rows), COMBINE_THREADS threads: thread (k, d) sums the ranges r = k, k + NS, ... of column d, NS = COMBINE_THREADS / D slices.
-template <int D>
-__global__ __launch_bounds__(COMBINE_THREADS) void attn_split_combine_kernel(const float *__restrict__ ml, const float *__restrict__ accw,
-                                                                         bf16_t *__restrict__ out, int nh, int nr) {
-    constexpr int NS = COMBINE_THREADS / D, NW = COMBINE_THREADS / 64;
-    __shared__ float w[SPLIT_MAX_RANGES];
-    __shared__ float red[2 * NW];
-    __shared__ float part[NS * D];
-    const int h = blockIdx.x, r = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t base = ((int64_t)r * nh + h) * nr;
-    const bool own = tid < nr;                                         // nr <= SPLIT_MAX_RANGES <= COMBINE_THREADS: one range per thread
-    const float m = own ? ml[(base + tid) * 2] : -INFINITY;
-    const float l = own ? ml[(base + tid) * 2 + 1] : 0.f;
-    const float mx = wave_max(m);
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    float M = red[0];
-#pragma unroll
-    for (int i = 1; i < NW; ++i) M = fmaxf(M, red[i]);
-    const float wr = m == -INFINITY ? 0.f : expf(m - M);             // a range without a visible key weighs nothing (no -inf - -inf)
-    if (own) w[tid] = wr;
-    const float wl = wave_sum(wr == 0.f ? 0.f : wr * l);
-    if (lane == 0) red[NW + wave] = wl;
-    __syncthreads();
-    float L = red[NW];
-#pragma unroll
-    for (int i = 1; i < NW; ++i) L += red[NW + i];
-    const int k = tid / D, d = tid - k * D;
-    float o = 0.f;
-#pragma unroll 8
-    for (int rg = k; rg < nr; rg += NS) {
-        const float wg = w[rg];
-        const float a = wg != 0.f ? accw[(base + rg) * D + d] : 0.f;  // nothing was written for an empty range
-        o = fmaf(wg, a, o);
-    }
-    part[k * D + d] = o;
-    __syncthreads();
-    if (tid < D) {
-        float t = part[tid];
-#pragma unroll
-        for (int i = 1; i < NS; ++i) t += part[i * D + tid];
-        out[((int64_t)r * nh + h) * D + tid] = f32_to_bf16(L > 0.f ? t * (1.f / L) : 0.f);     // no visible key at all: zeros
-    }
-}
-
-static int split_group(int nh, int nkv) {
-    const int G = nh / nkv;
-    return (G == 2 || G == 4 || G == 7) ? G : 1;
-}
-
-static bool split_shape_ok(int B, int S, int nh, int nkv, int maxlen, int D) {
-    return (D == 64 || D == 128) && B >= 1 && S >= 1 && S <= SPLIT_MAX_S && (int64_t)B * S <= 65535 && nkv >= 1 && nh >= nkv && nh % nkv == 0 &&
-           nh / split_group(nh, nkv) <= 65535 && maxlen >= 1 && maxlen <= SPLIT_MAXLEN;
-}
-
-static int64_t split_workspace_bytes(int B, int S, int nh, int maxlen, int D) {
-    const int64_t nr = cdiv(maxlen, SPLIT_RANGE);
-    return (int64_t)B * S * nh * nr * (D + 2) * 4;
 }
 
 static int attn_split(const char *who, const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, int64_t cs0, void *Kc, void *Vc,

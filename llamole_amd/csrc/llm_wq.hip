@@ -26,6 +26,7 @@
 //                     The image keeps the k order of the CODE lanes -- piece j of all lanes of a row is contiguous -- and the x image
 //                     uses the same order, which a dot product does not see; writes and fragment reads stay conflict-free.
 #include "common.h"
+#include "mx_quant.h"
 
 namespace ll {
 
@@ -44,31 +45,7 @@ __device__ __forceinline__ float wq_lo(uint32_t v) { return __uint_as_float(v <<
 __device__ __forceinline__ float wq_hi(uint32_t v) { return __uint_as_float(v & 0xffff0000u); }
 
 // ---------------------------------------------------------------------------------------------------------------- quantiser
-// shared exponent of a block from the bf16 bits of its amax (sign cleared): amax = m * 2^x, elem_max = M * 2^p -> e = x - p + (m > M)
-template <int BITS> __device__ __forceinline__ int wq_block_exp(uint32_t amax_bits) {
-    if (amax_bits == 0) return 0;
-    constexpr int P = BITS == 8 ? 8 : 2, THR = BITS == 8 ? 0x60 : 0x40, LO = BITS == 8 ? -117 : -125, HI = BITS == 8 ? 119 : 125;
-    int e = (int)(amax_bits >> 7) - 127 - P + ((int)(amax_bits & 0x7f) > THR ? 1 : 0);
-    return e < LO ? LO : (e > HI ? HI : e);
-}
-// a >= 0 (already divided by the scale) -> code without the sign bit; *grid = the grid value it stands for.  Round to nearest, ties to even.
-template <int BITS> __device__ __forceinline__ uint32_t wq_encode(float a, float *grid) {
-    constexpr float MAXV = BITS == 8 ? 448.f : 6.f, MINN = BITS == 8 ? 0.015625f : 1.f, SUB = BITS == 8 ? 512.f : 2.f;
-    constexpr int MB = BITS == 8 ? 3 : 1, EB = BITS == 8 ? 7 : 1;       // mantissa bits, exponent bias
-    a = fminf(a, MAXV);
-    if (a < MINN) {                    // subnormal grid: multiples of 2^-9 (0.5); rintf rounds half to even
-        const float q = rintf(a * SUB);
-        *grid = q / SUB;
-        return (uint32_t)q;            // q == SUB * MINN is the smallest normal code
-    }
-    uint32_t b = __float_as_uint(a);
-    constexpr uint32_t DROP = 23 - MB;
-    b += ((1u << (DROP - 1)) - 1u) + ((b >> DROP) & 1u);
-    b &= ~((1u << DROP) - 1u);
-    *grid = __uint_as_float(b);
-    return (((b >> 23) - 127 + EB) << MB) | ((b >> DROP) & ((1u << MB) - 1u));
-}
-
+// (wq_block_exp and wq_encode: mx_quant.h)
 // four lanes per block of 32 elements (16 B of bf16 each): coalesced reads and writes; Wdq may alias W (a lane writes what it alone read;
 // neither pointer is __restrict__)
 template <int BITS>

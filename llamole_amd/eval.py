@@ -52,6 +52,8 @@ def load_yaml_args(path: str, overrides: Optional[Dict[str, Any]] = None):
         flash_attn=cfg.get("flash_attn", "auto"),
         # reference hparams/model_args.py:112: 4 | 8 (there: bitsandbytes; here: the MX weight formats of llm_quant.py)
         quantization_bit=cfg.get("quantization_bit"),
+        # the KV cache of the decode: absent / null = bf16, "mxfp8" = kv_cache.MX8StaticCache (opt-in)
+        kv_cache_dtype=cfg.get("kv_cache_dtype"),
         # reference hparams/model_args.py:128: linear | dynamic, applied to the LLM config before the weights are loaded (rope.configure_rope)
         rope_scaling=cfg.get("rope_scaling"))
     data_args = SimpleNamespace(dataset=cfg.get("dataset"), dataset_dir=cfg.get("dataset_dir", "data"),
@@ -210,6 +212,8 @@ def run_eval(config_path: str, overrides: Optional[Dict[str, Any]] = None) -> Di
     quantization_bit = check_quantization_bit(model_args.quantization_bit)      # refused before anything is loaded
     from .rope import check_rope_scaling
     check_rope_scaling(model_args.rope_scaling)
+    from .kv_cache import check_kv_cache
+    kv_cache = check_kv_cache(model_args.kv_cache_dtype)                        # likewise
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     from .distributed import force_dist
     if world > 1 or force_dist():
@@ -237,7 +241,7 @@ def run_eval(config_path: str, overrides: Optional[Dict[str, Any]] = None) -> Di
     model = GraphLLMForCausalMLM.from_pretrained(tokenizer, model_args, data_args, training_args, finetuning_args,
                                                  load_adapter=bool(model_args.adapter_name_or_path))
     model.eval()
-    accel = model.enable_mi355x_decode(quantization_bit=quantization_bit)      # from_pretrained merged the adapter: the merged weights are rounded
+    accel = model.enable_mi355x_decode(quantization_bit=quantization_bit, kv_cache=kv_cache)      # from_pretrained merged the adapter: the merged weights are rounded
     model.batch_retro = bool(getattr(generating_args, "batch_retro", False) or (overrides or {}).get("batch_retro", False))
     if rank == 0:
         print(json.dumps({"llm_acceleration": accel}))

@@ -606,6 +606,21 @@ def fuse_cache_update(cache) -> int:
     return len(layers)
 
 
+def _is_kv8(cl) -> bool:
+    """Whether a cache layer holds MX8 codes (kv_cache.MX8StaticLayer: uint8 ``keys`` / ``values`` with ``key_scales`` / ``value_scales``)."""
+    keys = getattr(cl, "keys", None)
+    return keys is not None and keys.dtype == torch.uint8 and hasattr(cl, "key_scales")
+
+
+def _kv_layer_ok(cl) -> bool:
+    """A cache layer the fused attention entries take: contiguous bf16 K / V, or the four contiguous tensors of an MX8 layer."""
+    if not (cl.keys.is_contiguous() and cl.values.is_contiguous()):
+        return False
+    if _is_kv8(cl):
+        return cl.key_scales.is_contiguous() and cl.value_scales.is_contiguous()
+    return cl.keys.dtype == torch.bfloat16
+
+
 # ------------------------------------------------------------------------------------------ whole decoder layer = 5 launches
 class _FusedLayer:
     """Decode-step state of one HF decoder layer (Qwen2 / Llama / Mistral layout): concatenated q|k|v and gate|up weights
@@ -696,10 +711,9 @@ class _FusedLayer:
         if layers is None or self.layer_idx >= len(layers):
             return False
         cl = layers[self.layer_idx]
-        if not (getattr(cl, "_ll_fused_update", False) and cl.keys.dtype == torch.bfloat16 and cl.keys.is_contiguous()
-                and cl.values.is_contiguous()):
+        if not (getattr(cl, "_ll_fused_update", False) and _kv_layer_ok(cl)):
             return False
-        if not self.attn_serves(h.shape[0], 1, cl.keys.shape[2]):
+        if not self.attn_serves(h.shape[0], 1, cl.keys.shape[2], _is_kv8(cl)):
             return False
         cos = pe[0]
         return (mask.dtype == torch.bool and mask.dim() == 4 and mask.shape[1] == 1 and mask.shape[2] == 1
@@ -741,10 +755,11 @@ class _FusedLayer:
             _lib.check(rc, "ll_gemv_fused_bf16")
         return out
 
-    def attn_serves(self, B: int, S: int, maxlen: int) -> bool:
+    def attn_serves(self, B: int, S: int, maxlen: int, kv8: bool = False) -> bool:
         """Whether this layer's attention entry points take a static cache of ``maxlen`` slots for B sequences of S new positions: up to
-        ATTN_MAXLEN the one-workgroup kernels, beyond it whatever the key-split entry accepts (its own answer, asked once per shape)."""
-        if maxlen <= ATTN_MAXLEN:
+        ATTN_MAXLEN the one-workgroup kernels, beyond it whatever the key-split entry accepts (its own answer, asked once per shape).  An MX8
+        cache (``kv8``) has the key-split entries only, at every length, with the same bounds."""
+        if maxlen <= ATTN_MAXLEN and not kv8:
             return True
         key = (B, S, maxlen)
         if key not in self._split_ok:
@@ -776,7 +791,11 @@ class _FusedLayer:
         args = (qkv.data_ptr(), nqkv, cos.data_ptr(), sin.data_ptr(), 0 if cos.shape[0] == 1 else cos.stride(0), cl.keys.data_ptr(),
                 cl.values.data_ptr(), pos.data_ptr(), mask.data_ptr(), mask.stride(0), att.data_ptr(), B, self.nh, self.nkv,
                 cl.keys.shape[2], self.D, self.scaling)
-        if cl.keys.shape[2] > ATTN_MAXLEN:        # beyond the one-workgroup kernels: the keys split over workgroups, two launches
+        if _is_kv8(cl):                           # an MX8 cache: the key-split attention on codes and scales, at every length
+            name = "ll_decode_attn_rope_kv8"
+            rc = self.lib.ll_decode_attn_rope_kv8(*args[:5], cl.keys.data_ptr(), cl.key_scales.data_ptr(), cl.values.data_ptr(),
+                                                  cl.value_scales.data_ptr(), *args[7:], *self._split_tail(B, 1, cl.keys.shape[2], device))
+        elif cl.keys.shape[2] > ATTN_MAXLEN:      # beyond the one-workgroup kernels: the keys split over workgroups, two launches
             name = "ll_decode_attn_rope_split_bf16"
             rc = self.lib.ll_decode_attn_rope_split_bf16(*args, *self._split_tail(B, 1, cl.keys.shape[2], device))
         elif self.qn is not None:
@@ -843,7 +862,11 @@ class _FusedLayer:
         att = torch.empty(R, self.nq, dtype=torch.bfloat16, device=h.device)
         args = (qkv.data_ptr(), nqkv, cos.data_ptr(), sin.data_ptr(), cl.keys.data_ptr(), cl.values.data_ptr(), pos.data_ptr(), mask.data_ptr(),
                 att.data_ptr(), B, S, self.nh, self.nkv, cl.keys.shape[2], self.D, self.scaling)
-        if cl.keys.shape[2] > ATTN_MAXLEN:
+        if _is_kv8(cl):
+            name = "ll_suffix_attn_rope_kv8"
+            rc = self.lib.ll_suffix_attn_rope_kv8(*args[:4], cl.keys.data_ptr(), cl.key_scales.data_ptr(), cl.values.data_ptr(),
+                                                  cl.value_scales.data_ptr(), *args[6:], *self._split_tail(B, S, cl.keys.shape[2], h.device))
+        elif cl.keys.shape[2] > ATTN_MAXLEN:
             name = "ll_suffix_attn_rope_split_bf16"
             rc = self.lib.ll_suffix_attn_rope_split_bf16(*args, *self._split_tail(B, S, cl.keys.shape[2], h.device))
         elif self.qn is not None:
@@ -1129,8 +1152,8 @@ def _model_forward(self, input_ids=None, attention_mask=None, position_ids=None,
             and position_ids.dtype == torch.long and not kwargs.get("output_hidden_states") and not kwargs.get("output_attentions")
             and getattr(past_key_values, "layers", None) and all(getattr(l, "_ll_fused_update", False) for l in past_key_values.layers)
             and attention_mask.shape[1] == past_key_values.layers[0].keys.shape[2]
-            and past_key_values.layers[0].keys.dtype == torch.bfloat16
-            and layers[0]._ll_fused.attn_serves(input_ids.shape[0], 1, attention_mask.shape[1])):
+            and (past_key_values.layers[0].keys.dtype == torch.bfloat16 or _is_kv8(past_key_values.layers[0]))
+            and layers[0]._ll_fused.attn_serves(input_ids.shape[0], 1, attention_mask.shape[1], _is_kv8(past_key_values.layers[0]))):
         B, maxlen, D = input_ids.shape[0], attention_mask.shape[1], st["D"]
         dev = input_ids.device
         h = self.embed_tokens(input_ids)
@@ -1178,8 +1201,8 @@ def _model_forward(self, input_ids=None, attention_mask=None, position_ids=None,
     clayers = getattr(past_key_values, "layers", None)
     keys = getattr(clayers[0], "keys", None) if clayers else None
     if input_ids is not None and input_ids.dim() == 2 and input_ids.shape[1] <= MAX_APPEND_ROWS and keys is not None and keys.dim() == 4 \
-            and keys.shape[2] > ATTN_MAXLEN \
-            and not layers[0]._ll_fused.attn_serves(input_ids.shape[0], input_ids.shape[1], keys.shape[2]):
+            and (keys.shape[2] > ATTN_MAXLEN or _is_kv8(clayers[0])) \
+            and not layers[0]._ll_fused.attn_serves(input_ids.shape[0], input_ids.shape[1], keys.shape[2], _is_kv8(clayers[0])):
         st["declined"] = (f"decoder_layers: a static cache of {keys.shape[2]} slots ({input_ids.shape[0]} x {input_ids.shape[1]} new positions) is "
                           f"outside the bounds of the key-split attention (at most {ATTN_SPLIT_MAXLEN} slots, {MAX_STREAM_ROWS} sequences at decode)")
     return self._ll_model_orig(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
@@ -1197,11 +1220,12 @@ def _suffix_forward(self, st, layers, input_ids, attention_mask, position_ids, c
     if not (S >= 2 and FMA_GEMV_ROWS < R <= MAX_ROWS16 and input_ids.is_cuda and not torch.is_grad_enabled() and clayers
             and all(getattr(l, "_ll_fused_update", False) for l in clayers) and attention_mask is not None and attention_mask.dim() == 2
             and attention_mask.dtype == torch.long and attention_mask.stride(1) == 1 and attention_mask.shape[0] == B
-            and attention_mask.shape[1] == clayers[0].keys.shape[2] and clayers[0].keys.dtype == torch.bfloat16
-            and clayers[0].keys.is_contiguous() and clayers[0].values.is_contiguous() and clayers[0].keys.shape[0] == B
+            and attention_mask.shape[1] == clayers[0].keys.shape[2] and _kv_layer_ok(clayers[0])
+            and clayers[0].keys.shape[0] == B
             and position_ids is not None and position_ids.shape == input_ids.shape and position_ids.dtype == torch.long
             and not kwargs.get("output_hidden_states") and not kwargs.get("output_attentions")
-            and all(l._ll_fused.stream_ok for l in layers) and layers[0]._ll_fused.attn_serves(B, S, attention_mask.shape[1])):
+            and all(l._ll_fused.stream_ok for l in layers)
+            and layers[0]._ll_fused.attn_serves(B, S, attention_mask.shape[1], _is_kv8(clayers[0]))):
         return None
     h = self.embed_tokens(input_ids)
     if h.dtype != torch.bfloat16 or not h.is_contiguous():

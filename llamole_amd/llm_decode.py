@@ -115,8 +115,16 @@ MAX_HIP_BEAMS, MAX_HIP_BEAM_K, MAX_HIP_BEAM_NK, MAX_HIP_BEAM_TOPK = 16, 512, 409
 
 
 class GraphedDecoder:
-    def __init__(self, model, use_graph: bool = True, sync_every: int = 16, fused_cache: bool = False, sampler: str = "hip"):
+    def __init__(self, model, use_graph: bool = True, sync_every: int = 16, fused_cache: bool = False, sampler: str = "hip",
+                 kv_cache: Optional[str] = None):
         self.model = model
+        # None: transformers' bf16 StaticCache.  "mxfp8": kv_cache.MX8StaticCache -- FP8 E4M3 codes with one E8M0 scale per 32 elements of
+        # head_dim, 0.516 of the bytes; the fused layers then run ll_decode_attn_rope_kv8 / ll_suffix_attn_rope_kv8, HF's modules a dequantised
+        # staging pair.  Opt-in, never a default; the environment variable LLAMOLE_KV_CACHE is the A/B switch (like LLAMOLE_QUANT_BITS).
+        from .kv_cache import check_kv_cache
+        if kv_cache is None and os.environ.get("LLAMOLE_KV_CACHE"):
+            kv_cache = os.environ["LLAMOLE_KV_CACHE"]
+        self.kv_cache = check_kv_cache(kv_cache)
         self.use_graph = use_graph and next(model.parameters()).is_cuda
         self.sync_every = sync_every
         self.fused_cache = fused_cache    # one fused KV-append launch per layer (llm_accel.fuse_cache_update)
@@ -241,7 +249,12 @@ class GraphedDecoder:
             return
         self._key = key
         cfg = self.model.config
-        self.cache = StaticCache(config=cfg, max_cache_len=max_len)
+        if self.kv_cache == "mxfp8":
+            from .kv_cache import MX8StaticCache
+            on_device = torch.device(device).type == "cuda"
+            self.cache = MX8StaticCache(cfg, B, max_len, device, torch.bfloat16 if on_device else next(self.model.parameters()).dtype)
+        else:
+            self.cache = StaticCache(config=cfg, max_cache_len=max_len)
         self.tok = torch.zeros(B, 1, dtype=torch.long, device=device)
         self.pos = torch.zeros(1, dtype=torch.long, device=device)
         self.mask = torch.zeros(B, max_len, dtype=torch.long, device=device)
@@ -257,7 +270,8 @@ class GraphedDecoder:
         self._beam_key = None           # beam search: state buffer (llm_beam.py) and the captured forward + beam step
         self._beam_graph = None
         self._graph = None
-        self._cache_fused = False
+        # an MX8 cache on the device follows the fused convention from its construction (every layer at layer 0's counter, advanced per forward)
+        self._cache_fused = self.kv_cache is not None and self.cache.shared_counter
         self._side_graphs = {}          # captured against the buffers above
 
     def _captured(self, key, statics, fn):
@@ -451,6 +465,9 @@ class GraphedDecoder:
         penalty = 1.0 if penalty is None else penalty
         if num_beams is not None and (isinstance(num_beams, bool) or num_beams != 1):
             nb, es = check_beam_options(num_beams, early_stopping)
+            if self.kv_cache is not None:
+                raise NotImplementedError(f"GraphedDecoder.generate does not implement num_beams > 1 together with kv_cache={self.kv_cache!r}: "
+                                          "the beam KV reorder is bf16-only (use kv_cache=None for beam search)")
             if penalty != 1.0:
                 raise NotImplementedError("GraphedDecoder.generate does not implement repetition_penalty together with num_beams > 1")
             _reject_unsupported_generation_options(other)

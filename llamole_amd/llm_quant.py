@@ -58,6 +58,21 @@ def decode_codes(codes: torch.Tensor, bits: int) -> torch.Tensor:
     return torch.where(sign == 1, -mag, mag)
 
 
+def encode_codes8(dq: torch.Tensor, scale_bytes: torch.Tensor) -> torch.Tensor:
+    """The inverse of ``decode_codes(., 8)`` on ``mx_round``'s output: dq [N, K] (values code * 2^e, on the grid: nothing is rounded here) and
+    the scale bytes [N, K / 32] -> the E4M3 code bytes [N, K] uint8.  The sign bit follows the sign of dq (of a zero as well, as the device
+    quantiser keeps it)."""
+    N, K = dq.shape
+    one = torch.ones((), dtype=torch.float32, device=dq.device)
+    e = scale_bytes.to(torch.int32) - 127
+    v = dq.float().reshape(N, K // BLOCK, BLOCK) * torch.ldexp(one, -e).unsqueeze(-1)      # exact: a power of two
+    a = v.abs().contiguous()
+    b = a.view(torch.int32)
+    normal = ((((b >> 23) & 0xff) - 127 + 7) << 3) | ((b >> 20) & 7)
+    code = torch.where(a < 2.0 ** -6, (a * 512.0).to(torch.int32), normal) | (torch.signbit(v).to(torch.int32) << 7)
+    return code.to(torch.uint8).reshape(N, K)
+
+
 def mx_round(w: torch.Tensor, bits: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """The quantiser in plain torch: w [N, K] (rounded to bf16 first) -> (w_dq f32 [N, K], scale bytes uint8 [N, K / 32]).  Works on CPU;
     the oracle of ``ll_wq_quantize_bf16`` and the CPU install path."""

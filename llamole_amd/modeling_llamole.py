@@ -71,11 +71,13 @@ class GraphLLMForCausalMLM(nn.Module):
         self.batch_values = True   # A* value estimates of one expansion in one LLM forward (estimate_synthesis_complexity_batch)
 
     def enable_graphed_decode(self, use_graph: bool = True, sync_every: int = 16, fused_cache: bool = False,
-                              reuse_query_kv: bool = True):
+                              reuse_query_kv: bool = True, kv_cache: Optional[str] = None):
         """Route every LLM decode of the path through one captured hipGraph of the stock HF forward; ``reuse_query_kv``
-        runs the query-token re-forward on top of the decode's KV cache whenever that is the same computation."""
+        runs the query-token re-forward on top of the decode's KV cache whenever that is the same computation.  ``kv_cache``: None (the
+        bf16 static cache) or "mxfp8" (kv_cache.MX8StaticCache)."""
         from .llm_decode import GraphedDecoder
-        self.decoder = GraphedDecoder(self.language_model, use_graph=use_graph, sync_every=sync_every, fused_cache=fused_cache)
+        self.decoder = GraphedDecoder(self.language_model, use_graph=use_graph, sync_every=sync_every, fused_cache=fused_cache,
+                                      kv_cache=kv_cache)
         self.reuse_query_kv = reuse_query_kv
         return self
 
@@ -83,10 +85,13 @@ class GraphLLMForCausalMLM(nn.Module):
         """The whole LLM-side stack in one call (what bench.py measures): HIP kernels under the HF modules
         (llm_accel.accelerate_llm) + hipGraph decode with the fused KV append and in-graph sampler.  Returns the report of
         what took effect; on a CPU model it only installs the (eager) static-cache decoder.  ``quantization_bit`` 8 | 4 rounds the
-        decoder-layer Linears onto the MX grid first (llm_quant.py; also on a CPU model) and decodes from the packed codes."""
+        decoder-layer Linears onto the MX grid first (llm_quant.py; also on a CPU model) and decodes from the packed codes.  ``kv_cache="mxfp8"``
+        (among ``kw``; or the environment variable LLAMOLE_KV_CACHE) decodes on the MX8 KV cache; the report names it only when it is on."""
         from .llm_accel import accelerate_llm
         info = accelerate_llm(self.language_model, quantization_bit=quantization_bit)
         self.enable_graphed_decode(use_graph=use_graph, fused_cache=bool(info.get("decode_attention")), **kw)
+        if self.decoder.kv_cache is not None:
+            info["kv_cache"] = self.decoder.kv_cache
         return info
 
     def _llm_generate(self, inputs=None, attention_mask=None, inputs_embeds=None, **kwargs):
