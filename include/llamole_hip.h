@@ -409,6 +409,35 @@ int64_t ll_linear_rows64_workspace_bytes(int M, int N);
 int ll_rows64_ssq_chunks(int N);
 int ll_rows64_prenorm_bf16(const void *x, int ldx, const void *norm_w, void *scaled_out, int ldn, float *ssq_out, int M, int N, void *stream);
 
+/* ---- the scaled residual epilogue and the scaled embedding (Granite layout: transformers models/granite/modeling_granite.py) -------------
+ * GraniteDecoderLayer.forward adds both of its sub-blocks to the residual stream as
+ *         hidden_states = residual + hidden_states * self.residual_multiplier
+ * on bf16 tensors with a Python float: the product is taken in f32 with the multiplier rounded to f32 and rounded to bf16, then the sum is.
+ * With the Linear's own rounding that is three roundings, and the epilogue restates them:
+ *     LL_GEMV_RESIDUAL_SCALED :  bf16( residual + bf16( bf16(acc + bias) * (float)residual_scale ) )
+ * residual_scale must be finite and non-zero (LL_EINVAL otherwise, nothing is launched); residual_scale == 1 gives the bits of
+ * LL_GEMV_RESIDUAL.  The epilogue is not a value of `epi`: it has entry points of its own, one per Linear family, and the entries above keep
+ * their signatures, their kernels and their arithmetic.  None takes an RMSNorm prologue (o_proj and down_proj have none):
+ *   ll_gemv_fused_rs_bf16    ll_gemv_fused_bf16 at LL_GEMV_RESIDUAL with norm_w = NULL: M in 1..4, the same FMA order, the same choice between
+ *                            the generic kernel and the one that stages x in LDS.
+ *   ll_linear_rows16_rs_bf16 ll_linear_rows16_bf16 at LL_GEMV_RESIDUAL with norm_w = NULL: M in 1..16, K % 32 == 0, the same geometry.
+ *   ll_linear_rows64_rs_bf16 ll_linear_rows64_bf16 at LL_GEMV_RESIDUAL: M in 1..64 on a packed weight, row_ssq / next_norm_w / workspace as
+ *                            there.  One launch without a workspace; with one, the slab sum applies bias, scale and residual, and
+ *                            scaled_out / ssq_out are made from the rounded scaled-residual row, as the next layer reads it.
+ * ll_embed_rows_bf16 : GraniteModel.forward's `inputs_embeds * self.embedding_multiplier` with the gather in front of it, one launch:
+ *     out[m, 0..H) = bf16( table[ids[m], 0..H) * (float)scale ) for ids [M] int64, table [V, H] bf16 (row stride ldt), out [M, H] (row stride
+ *     ldo); f32 product, ONE rounding.  H, ldt, ldo multiples of 8, table and out 16-byte aligned, 1 <= M <= 65535, scale finite and
+ *     non-zero (LL_EINVAL otherwise).  An id outside [0, V) is not an error: nothing is read for it and its row is written as zeros. */
+int ll_gemv_fused_rs_bf16(const void *x, int ldx, const void *W, int ldw, const float *bias, const void *residual, int ldr, void *out, int ldc,
+                          int M, int N, int K, float residual_scale, void *stream);
+int ll_linear_rows16_rs_bf16(const void *x, int ldx, const void *W, int ldw, const float *bias, const void *residual, int ldr, void *out,
+                             int ldc, int M, int N, int K, float residual_scale, void *stream);
+int ll_linear_rows64_rs_bf16(const void *x, int ldx, const void *Wp, const float *bias, const void *residual, int ldr, void *out, int ldc, int M,
+                             int N, int K, const float *row_ssq, int ssq_chunks, float eps, const void *next_norm_w, void *scaled_out, int ldn,
+                             float *ssq_out, void *workspace, int64_t workspace_bytes, float residual_scale, void *stream);
+int ll_embed_rows_bf16(const int64_t *ids, const void *table, int64_t ldt, void *out, int64_t ldo, int M, int V, int H, float scale,
+                       void *stream);
+
 /* ll_sample_token_bf16 : one decode-loop sampling step per row in ONE launch -- HF TemperatureLogitsWarper + TopPLogitsWarper
  *     + softmax + multinomial (transformers generation/logits_process.py, generation/utils.py _sample; the reference reaches
  *     them through language_model.generate(do_sample, temperature, top_p), modeling_llamole.py:599/:849) and the loop's

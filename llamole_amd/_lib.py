@@ -101,6 +101,10 @@ SIGNATURES = {
     "ll_rows64_ssq_chunks": (_I, [_I]),
     "ll_rows64_prenorm_bf16": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P]),
     "ll_linear_rows64_workspace_bytes": (_I64, [_I, _I]),
+    "ll_gemv_fused_rs_bf16": (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _F, _P]),
+    "ll_linear_rows16_rs_bf16": (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _F, _P]),
+    "ll_linear_rows64_rs_bf16": (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _I, _F, _P, _P, _I, _P, _P, _I64, _F, _P]),
+    "ll_embed_rows_bf16": (_I, [_P, _P, _I64, _P, _I64, _I, _I, _I, _F, _P]),
     "ll_gin_forward_train": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "ll_gin_backward_c": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "ll_sample_token_bf16": (_I, [_P, _I64, _I, _I, _F, _F, _I, _P, _P, _I, _I64, _P, _P, _P, _I64, _I, _P, _P, _P, _I, _P, _P]),

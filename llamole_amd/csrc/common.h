@@ -108,6 +108,12 @@ inline void debug_guard_check(const void *p, size_t n, const char *when) {      
 
 __host__ __device__ inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// a multiplier of the scaled residual epilogue / the embedding scale: finite and non-zero (inf * 0 and NaN fail the product test)
+inline bool scale_ok(float m) { return m != 0.f && m * 0.f == 0.f; }
+// The multiplier of a scaled residual epilogue reaches a kernel as a trailing parameter pack: empty in every instantiation without that
+// epilogue -- whose arguments and code are therefore what they were before the epilogue existed -- and one float in the scaled ones.
+__device__ __forceinline__ float pack_scale() { return 1.f; }
+__device__ __forceinline__ float pack_scale(float m) { return m; }
 
 // ---------------------------------------------------------------- device numerics
 __device__ __forceinline__ float bf16_to_f32(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }

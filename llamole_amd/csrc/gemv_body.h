@@ -12,7 +12,9 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float bfr2(float v) { return bf16_to_f32(f32_to_bf16(v)); }   // round through bf16
 
 // GEMV_SCALE (MoE down projection only): bf16( bf16(acc) * row_scale[m] ) -- the routing weight applied to the rounded expert output
-enum { GEMV_PLAIN = 0, GEMV_RESIDUAL = 1, GEMV_SILU_MUL = 2, GEMV_SCALE = 3 };
+// GEMV_RESIDUAL_SCALED (Granite layout, ll_gemv_fused_rs_bf16): bf16( residual + bf16( bf16(acc + bias) * row_scale[m] ) ) -- the layer's
+//     residual_multiplier (the same float in every row) applied to the rounded Linear output, as HF's `residual + hidden_states * m`
+enum { GEMV_PLAIN = 0, GEMV_RESIDUAL = 1, GEMV_SILU_MUL = 2, GEMV_SCALE = 3, GEMV_RESIDUAL_SCALED = 4 };
 // 16-byte weight loads per row in flight per lane at one token row (x 2 rows per wave).  Re-swept once the kernels were built with
 // kernel-argument preloading: 4 beats the earlier 8 (q|k|v 9.2 -> 8.2 us, LLM part of a molecule 353.6 -> 347.1 ms with the
 // plain GEMV of lm_head at 4 as well); the FMA order per output row does not depend on it.
@@ -71,7 +73,8 @@ __device__ __forceinline__ void gemv_fma(float (&acc)[MROWS][2], const u32x4 (&w
 // (GEMV_SILU_MUL: gate row n and up row n + N; otherwise rows 2w, 2w+1); a lane reads 16 B of each row per step with UNR steps in flight,
 // x comes from LDS (NORM: the workgroup normalises its MROWS rows once into xs [MROWS][K], with the first weight loads already in flight;
 // red [MROWS][4] is its reduction scratch) or from L1/L2.  f32 FMA chains in the lane/chunk order of gemv_bf16_kernel.
-// Token row m: x at xr[m], residual at rr[m] (GEMV_RESIDUAL), output at cr[m], routing weight rs[m] (GEMV_SCALE).
+// Token row m: x at xr[m], residual at rr[m] (GEMV_RESIDUAL, GEMV_RESIDUAL_SCALED), output at cr[m], routing weight / residual multiplier
+// rs[m] (GEMV_SCALE / GEMV_RESIDUAL_SCALED).
 // Every thread of the workgroup must call it (NORM has two barriers); a caller that calls it again puts a barrier in between (xs, red).
 template <int MROWS, bool NORM, int EPI, bool NT, int XC>
 __device__ __forceinline__ void gemv_fused_body(const bf16_t *const (&xr)[MROWS], const bf16_t *__restrict__ W, int ldw,
@@ -203,6 +206,7 @@ __device__ __forceinline__ void gemv_fused_body(const bf16_t *const (&xr)[MROWS]
                         float o = v[r] + (bias ? bias[n0 + r] : 0.f);
                         if (EPI == GEMV_RESIDUAL) o = bf16_to_f32(rr[m][n0 + r]) + bfr2(o);
                         if (EPI == GEMV_SCALE) o = bfr2(o) * rs[m];
+                        if (EPI == GEMV_RESIDUAL_SCALED) o = bf16_to_f32(rr[m][n0 + r]) + bfr2(bfr2(o) * rs[m]);
                         cr[m][n0 + r] = f32_to_bf16(o);
                     }
                 }

@@ -37,14 +37,38 @@ __global__ __launch_bounds__(256) void gemv_fused_kernel(const bf16_t *__restric
     gemv_fused_body<MROWS, NORM, EPI, NT, XC>(xr, W, ldw, bias, normw, eps, rr, cr, rs, N, K, blockIdx.x * 4 + (threadIdx.x >> 6), xs, red);
 }
 
+// The same GEMV with the scaled residual epilogue (GEMV_RESIDUAL_SCALED, Granite layout): a kernel of its own, so that the float is an
+// argument of this kernel alone and the instantiations above keep their arguments and their code.  No RMSNorm prologue: the Linears that
+// carry the residual add (o_proj, down_proj) have none.
+template <int MROWS, bool NT>
+__global__ __launch_bounds__(256) void gemv_fused_rs_kernel(const bf16_t *__restrict__ X, int ldx, const bf16_t *__restrict__ W, int ldw,
+                                                            const float *__restrict__ bias, const bf16_t *__restrict__ res, int ldr,
+                                                            bf16_t *__restrict__ C, int ldc, int N, int K, float rscale) {
+    __shared__ float red[MROWS][4];
+    const bf16_t *xr[MROWS], *rr[MROWS];
+    bf16_t *cr[MROWS];
+    float rs[MROWS];
+#pragma unroll
+    for (int m = 0; m < MROWS; ++m) {
+        xr[m] = X + (int64_t)m * ldx;
+        rr[m] = res + (int64_t)m * ldr;
+        cr[m] = C + (int64_t)m * ldc;
+        rs[m] = rscale;
+    }
+    gemv_fused_body<MROWS, false, GEMV_RESIDUAL_SCALED, NT, 2>(xr, W, ldw, bias, nullptr, 0.f, rr, cr, rs, N, K,
+                                                                blockIdx.x * 4 + (threadIdx.x >> 6), nullptr, red);
+}
+
 // gemv_fused_kernel's prologue-free form (down_proj: no RMSNorm, long K) for ONE token row with x staged in LDS: in the
 // generic kernel every wave re-reads its x chunks from L1/L2 next to the weight stream (8 more loads per lane and block,
 // 24 in flight); here the workgroup copies x into LDS once, with its first weight loads already in flight, and the stream
 // keeps 16 loads per lane.  Same FMA order per output row, so the result is bit-identical.
-template <int EPI>
+// RS: empty, or one float = the multiplier of GEMV_RESIDUAL_SCALED (pack_scale, common.h).
+template <int EPI, typename... RS>
 __global__ __launch_bounds__(256) void gemv_stage_kernel(const bf16_t *__restrict__ X, const bf16_t *__restrict__ W, int ldw,
                                                          const float *__restrict__ bias, const bf16_t *__restrict__ res,
-                                                         bf16_t *__restrict__ C, int N, int K) {
+                                                         bf16_t *__restrict__ C, int N, int K, RS... rscale) {
+    static_assert(sizeof...(RS) == (EPI == GEMV_RESIDUAL_SCALED ? 1 : 0), "the scale is an argument of the scaled epilogue alone");
     constexpr int R = 2, UNR = LL_GEMV_STAGE_UNR, XCS = 10;       // XCS 16-byte chunks of x per thread: K <= 20480
     extern __shared__ __attribute__((aligned(16))) unsigned char sm_gemvs[];
     bf16_t *xs = reinterpret_cast<bf16_t *>(sm_gemvs);
@@ -86,6 +110,7 @@ __global__ __launch_bounds__(256) void gemv_stage_kernel(const bf16_t *__restric
             if (n0 + r < N) {
                 float o = v[r] + (bias ? bias[n0 + r] : 0.f);
                 if (EPI == GEMV_RESIDUAL) o = bf16_to_f32(res[n0 + r]) + bfr2(o);
+                if (EPI == GEMV_RESIDUAL_SCALED) o = bf16_to_f32(res[n0 + r]) + bfr2(bfr2(o) * pack_scale(rscale...));
                 C[n0 + r] = f32_to_bf16(o);
             }
         }
@@ -222,6 +247,37 @@ static int gemv_fused(bool nt, const void *x, int ldx, const void *W, int ldw, c
     }
 }
 
+// ll_gemv_fused_rs_bf16: the shapes and the kernel choice of gemv_fused at LL_GEMV_RESIDUAL without a norm, on the scaled instantiations
+static int gemv_fused_rs(bool nt, const void *x, int ldx, const void *W, int ldw, const float *bias, const void *residual, int ldr, void *out,
+                         int ldc, int M, int N, int K, float rscale, hipStream_t s) {
+    LL_CHECK(x && W && out && residual, "ll_gemv_fused_rs_bf16: null argument");
+    LL_CHECK(M >= 1 && M <= 4, "ll_gemv_fused_rs_bf16: M=%d rows (decode shapes only, 1..4)", M);
+    LL_CHECK(N >= 1 && K >= 8 && K % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0, "ll_gemv_fused_rs_bf16: K, ldx, ldw must be multiples of 8");
+    LL_CHECK(scale_ok(rscale), "ll_gemv_fused_rs_bf16: residual_scale must be finite and non-zero");
+    const bf16_t *X = (const bf16_t *)x, *Wt = (const bf16_t *)W, *rs = (const bf16_t *)residual;
+    bf16_t *C = (bf16_t *)out;
+    const dim3 grid(cdiv(N, 8));
+    if (g_gemv_stage && nt && M == 1 && K >= 8192 && K <= 20480) {
+        hipLaunchKernelGGL((gemv_stage_kernel<GEMV_RESIDUAL_SCALED, float>), grid, dim3(256), (size_t)K * 2, s, X, Wt, ldw, bias, rs, C, N, K, rscale);
+        LL_LAUNCH_CHECK();
+        return LL_OK;
+    }
+#define LL_GRS(M_)                                                                                                                          \
+    do {                                                                                                                                    \
+        if (nt) hipLaunchKernelGGL((gemv_fused_rs_kernel<M_, true>), grid, dim3(256), 0, s, X, ldx, Wt, ldw, bias, rs, ldr, C, ldc, N, K, rscale); \
+        else hipLaunchKernelGGL((gemv_fused_rs_kernel<M_, false>), grid, dim3(256), 0, s, X, ldx, Wt, ldw, bias, rs, ldr, C, ldc, N, K, rscale);  \
+    } while (0)
+    switch (M) {
+        case 1: LL_GRS(1); break;
+        case 2: LL_GRS(2); break;
+        case 3: LL_GRS(3); break;
+        default: LL_GRS(4); break;
+    }
+#undef LL_GRS
+    LL_LAUNCH_CHECK();
+    return LL_OK;
+}
+
 }  // namespace ll
 
 using namespace ll;
@@ -231,6 +287,11 @@ extern "C" {
 int ll_gemv_fused_bf16(const void *x, int ldx, const void *W, int ldw, const float *bias, const void *norm_w, float eps,
                        const void *residual, int ldr, void *out, int ldc, int M, int N, int K, int epi, void *stream) {
     return gemv_fused(g_gemv_nt != 0, x, ldx, W, ldw, bias, norm_w, eps, residual, ldr, out, ldc, M, N, K, epi, (hipStream_t)stream);
+}
+
+int ll_gemv_fused_rs_bf16(const void *x, int ldx, const void *W, int ldw, const float *bias, const void *residual, int ldr, void *out, int ldc,
+                          int M, int N, int K, float residual_scale, void *stream) {
+    return gemv_fused_rs(g_gemv_nt != 0, x, ldx, W, ldw, bias, residual, ldr, out, ldc, M, N, K, residual_scale, (hipStream_t)stream);
 }
 
 int ll_decode_prologue(const int64_t *position_ids, const float *inv_freq, float attention_scaling, const int64_t *mask2d,

@@ -127,6 +127,29 @@ __global__ __launch_bounds__(64) void kv_append_bf16_kernel(bf16_t *__restrict__
     }
 }
 
+// Embedding gather and scale in one launch (Granite layout: GraniteModel.forward multiplies the gathered rows by embedding_multiplier):
+// out[m, :] = bf16(table[ids[m], :] * scale), f32 product, one rounding -- torch's bf16 tensor times a Python float.  grid (M, H / 2048
+// rounded up), 256 threads x 16 bytes.  An id outside [0, V) reads nothing and gives a row of zeros.
+__global__ __launch_bounds__(256) void embed_rows_bf16_kernel(const long long *__restrict__ ids, const bf16_t *__restrict__ table, int64_t ldt,
+                                                               bf16_t *__restrict__ out, int64_t ldo, int V, int H8, float scale) {
+    const int m = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+    if (c >= H8) return;
+    const long long id = ids[m];
+    uint4 o = make_uint4(0, 0, 0, 0);
+    if (id >= 0 && id < V) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(table + id * ldt + c * 8);
+        const uint32_t in[4] = {v.x, v.y, v.z, v.w};
+        uint32_t r[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float a = __uint_as_float(in[t] << 16) * scale, b = __uint_as_float(in[t] & 0xffff0000u) * scale;
+            r[t] = (uint32_t)f32_to_bf16(a) | ((uint32_t)f32_to_bf16(b) << 16);
+        }
+        o = make_uint4(r[0], r[1], r[2], r[3]);
+    }
+    *reinterpret_cast<uint4 *>(out + (int64_t)m * ldo + c * 8) = o;
+}
+
 }  // namespace ll
 
 using namespace ll;
@@ -173,6 +196,19 @@ int ll_kv_append_bf16(void *K, void *V, const void *k_new, const void *v_new, co
     hipLaunchKernelGGL(kv_append_bf16_kernel, dim3(B * nkv * S), dim3(64), 0, (hipStream_t)stream, (bf16_t *)K, (bf16_t *)V,
                        (const bf16_t *)k_new, (const bf16_t *)v_new, (const long long *)pos, nkv, S, maxlen, D, kstr[0], kstr[1],
                        kstr[2], vstr[0], vstr[1], vstr[2]);
+    LL_LAUNCH_CHECK();
+    return LL_OK;
+}
+
+int ll_embed_rows_bf16(const int64_t *ids, const void *table, int64_t ldt, void *out, int64_t ldo, int M, int V, int H, float scale,
+                       void *stream) {
+    LL_CHECK(ids && table && out, "ll_embed_rows_bf16: null argument");
+    LL_CHECK(M >= 1 && M <= 65535 && V >= 1 && H >= 8 && H % 8 == 0 && ldt % 8 == 0 && ldo % 8 == 0 && ldt >= H && ldo >= H,
+             "ll_embed_rows_bf16: 1 <= M <= 65535, H and the row strides multiples of 8, strides >= H");
+    LL_CHECK(((uintptr_t)table & 15) == 0 && ((uintptr_t)out & 15) == 0, "ll_embed_rows_bf16: table and out must be 16-byte aligned");
+    LL_CHECK(scale_ok(scale), "ll_embed_rows_bf16: scale must be finite and non-zero");
+    hipLaunchKernelGGL(embed_rows_bf16_kernel, dim3(M, cdiv(H / 8, 256)), dim3(256), 0, (hipStream_t)stream, (const long long *)ids,
+                       (const bf16_t *)table, ldt, (bf16_t *)out, ldo, V, H / 8, scale);
     LL_LAUNCH_CHECK();
     return LL_OK;
 }

@@ -26,15 +26,18 @@ typedef uint32_t r16_u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((ext_vector_type(8))) __bf16 r16_bf16x8;
 typedef __attribute__((ext_vector_type(4))) float r16_f32x4;
 
-enum { R16_PLAIN = 0, R16_RESIDUAL = 1, R16_SILU_MUL = 2 };
+// R16_RESIDUAL_SCALED (ll_linear_rows16_rs_bf16, Granite layout): bf16(residual + bf16(bf16(acc + bias) * rscale))
+enum { R16_PLAIN = 0, R16_RESIDUAL = 1, R16_SILU_MUL = 2, R16_RESIDUAL_SCALED = 3 };
 
 __device__ __forceinline__ float r16_bfr(float v) { return bf16_to_f32(f32_to_bf16(v)); }
 
-template <int EPI, int SEG, bool NORM>
+// RS: empty, or one float = the multiplier of R16_RESIDUAL_SCALED (pack_scale, common.h).
+template <int EPI, int SEG, bool NORM, typename... RS>
 __global__ __launch_bounds__(512) void rows16_kernel(const bf16_t *__restrict__ X, int ldx, const bf16_t *__restrict__ W, int ldw,
                                                      const float *__restrict__ bias, const bf16_t *__restrict__ normw, float eps,
                                                      const bf16_t *__restrict__ res, int ldr, void *__restrict__ Cv, int ldc, int M,
-                                                     int N, int K, int ksplit, int out_f32) {
+                                                     int N, int K, int ksplit, int out_f32, RS... rscale) {
+    static_assert(sizeof...(RS) == (EPI == R16_RESIDUAL_SCALED ? 1 : 0), "the scale is an argument of the scaled epilogue alone");
     constexpr int NT = EPI == R16_SILU_MUL ? 2 : 1;     // weight sub-tiles per wave (gate rows + the matching up rows)
     // SEG = bytes of a row per block (128 | 256 | 512)
     constexpr int PITCH = SEG + 16;                     // LDS row pitch: (PITCH / 4) % 64 == 4 -> 16 rows cover the 64 banks once
@@ -187,6 +190,7 @@ __global__ __launch_bounds__(512) void rows16_kernel(const bf16_t *__restrict__ 
         } else {
             float v = acc[0][j] + ((bias && ok) ? bias[n] : 0.f);
             if (EPI == R16_RESIDUAL) v = (ok ? bf16_to_f32(res[(int64_t)m * ldr + n]) : 0.f) + r16_bfr(v);
+            if (EPI == R16_RESIDUAL_SCALED) v = (ok ? bf16_to_f32(res[(int64_t)m * ldr + n]) : 0.f) + r16_bfr(r16_bfr(v) * pack_scale(rscale...));
             o[j] = f32_to_bf16(v);
         }
     }
@@ -216,26 +220,62 @@ static int launch_rows16_seg(int waves, int ksplit, hipStream_t s, const bf16_t 
     return LL_OK;
 }
 
-template <int EPI, bool NORM>
-static int launch_rows16(hipStream_t s, const bf16_t *X, int ldx, const bf16_t *W, int ldw, const float *bias, const bf16_t *normw, float eps,
-                         const bf16_t *res, int ldr, void *C, int ldc, int M, int N, int K, int out_f32) {
+// (segment bytes, waves per workgroup, K slices) of a launch: the tuning override, else by tile count
+static void rows16_geometry(bool gated, int N, int &seg, int &waves, int &ksplit) {
     const int ntiles = (N + 15) / 16;
-    int seg, waves, ksplit;
     if (g_rows16_geom) {
         seg = g_rows16_geom >> 16, waves = (g_rows16_geom >> 8) & 255, ksplit = g_rows16_geom & 255;
     } else {
         // enough waves to hide the load -> LDS -> MFMA latency chain of each one: split K until tiles x ksplit >= ~14 per CU
         // (tools/rows16_sweep.py: gate|up 4 waves x ksplit 4, q|k|v / o_proj / down_proj 8 x 8, lm_head 4 x 1)
-        seg = EPI == R16_SILU_MUL ? 256 : 512;
+        seg = gated ? 256 : 512;
         ksplit = 1;
         while (ksplit < 8 && ntiles * ksplit < 3500) ksplit *= 2;
         waves = ksplit <= 4 ? 4 : 8;
         if (ksplit == 8 && ntiles * 4 >= 1100) seg = 256, waves = 4, ksplit = 4;      // q|k|v (288 tiles): 11.1 us vs 12.5
         if (ksplit == 1) seg = 256, ksplit = 2;     // thousands of tiles (lm_head, GIN template head): 4 x 2 beats 4 x 1 (127 vs 141 us on the head)
     }
+}
+
+template <int EPI, bool NORM>
+static int launch_rows16(hipStream_t s, const bf16_t *X, int ldx, const bf16_t *W, int ldw, const float *bias, const bf16_t *normw, float eps,
+                         const bf16_t *res, int ldr, void *C, int ldc, int M, int N, int K, int out_f32) {
+    int seg, waves, ksplit;
+    rows16_geometry(EPI == R16_SILU_MUL, N, seg, waves, ksplit);
     if (seg == 128) return launch_rows16_seg<EPI, 128, NORM>(waves, ksplit, s, X, ldx, W, ldw, bias, normw, eps, res, ldr, C, ldc, M, N, K, out_f32);
     if (seg == 256) return launch_rows16_seg<EPI, 256, NORM>(waves, ksplit, s, X, ldx, W, ldw, bias, normw, eps, res, ldr, C, ldc, M, N, K, out_f32);
     return launch_rows16_seg<EPI, 512, NORM>(waves, ksplit, s, X, ldx, W, ldw, bias, normw, eps, res, ldr, C, ldc, M, N, K, out_f32);
+}
+
+template <int SEG>
+static int launch_rows16_rs_seg(int waves, int ksplit, hipStream_t s, const bf16_t *X, int ldx, const bf16_t *W, int ldw, const float *bias,
+                                const bf16_t *res, int ldr, void *C, int ldc, int M, int N, int K, float rscale) {
+    const int ntiles = (N + 15) / 16;
+    const size_t lds = (size_t)waves * 2 * 16 * (SEG + 16);
+    LL_CHECK(lds <= 160 * 1024, "ll_linear_rows16_rs_bf16: %d waves x %d-byte segments need %zu bytes of LDS", waves, SEG, lds);
+    LL_TRY((allow_dynamic_lds<rows16_kernel<R16_RESIDUAL_SCALED, SEG, false, float>>(lds)));
+    const int tpw = waves / ksplit;
+    hipLaunchKernelGGL((rows16_kernel<R16_RESIDUAL_SCALED, SEG, false, float>), dim3((ntiles + tpw - 1) / tpw), dim3(waves * 64), lds, s, X, ldx,
+                       W, ldw, bias, (const bf16_t *)nullptr, 0.f, res, ldr, C, ldc, M, N, K, ksplit, 0, rscale);
+    return LL_OK;
+}
+
+// ll_linear_rows16_rs_bf16: the shapes and the geometry of linear_rows16_launch at the residual epilogue without a norm
+static int linear_rows16_rs_launch(const void *x, int ldx, const void *W, int ldw, const float *bias, const void *residual, int ldr, void *out,
+                                   int ldc, int M, int N, int K, float rscale, hipStream_t s) {
+    LL_CHECK(x && W && out && residual, "ll_linear_rows16_rs_bf16: null argument");
+    LL_CHECK(M >= 1 && M <= 16, "ll_linear_rows16_rs_bf16: M=%d rows (1..16)", M);
+    LL_CHECK(N >= 1 && K >= 32 && K % 32 == 0 && ldx % 8 == 0 && ldw % 8 == 0, "ll_linear_rows16_rs_bf16: K must be a multiple of 32, ldx / ldw of 8");
+    LL_CHECK(((uintptr_t)x & 15) == 0 && ((uintptr_t)W & 15) == 0, "ll_linear_rows16_rs_bf16: operands must be 16-byte aligned");
+    LL_CHECK(scale_ok(rscale), "ll_linear_rows16_rs_bf16: residual_scale must be finite and non-zero");
+    const bf16_t *X = (const bf16_t *)x, *Wt = (const bf16_t *)W, *rs = (const bf16_t *)residual;
+    int seg, waves, ksplit;
+    rows16_geometry(false, N, seg, waves, ksplit);
+    if (seg == 128) LL_TRY((launch_rows16_rs_seg<128>(waves, ksplit, s, X, ldx, Wt, ldw, bias, rs, ldr, out, ldc, M, N, K, rscale)));
+    else if (seg == 256) LL_TRY((launch_rows16_rs_seg<256>(waves, ksplit, s, X, ldx, Wt, ldw, bias, rs, ldr, out, ldc, M, N, K, rscale)));
+    else LL_TRY((launch_rows16_rs_seg<512>(waves, ksplit, s, X, ldx, Wt, ldw, bias, rs, ldr, out, ldc, M, N, K, rscale)));
+    LL_LAUNCH_CHECK();
+    return LL_OK;
 }
 
 int linear_rows16_launch(const void *x, int ldx, const void *W, int ldw, const float *bias, const void *norm_w, float eps,
@@ -272,6 +312,11 @@ extern "C" {
 int ll_linear_rows16_bf16(const void *x, int ldx, const void *W, int ldw, const float *bias, const void *norm_w, float eps,
                           const void *residual, int ldr, void *out, int ldc, int M, int N, int K, int epi, void *stream) {
     return linear_rows16_launch(x, ldx, W, ldw, bias, norm_w, eps, residual, ldr, out, ldc, M, N, K, epi, 0, (hipStream_t)stream);
+}
+
+int ll_linear_rows16_rs_bf16(const void *x, int ldx, const void *W, int ldw, const float *bias, const void *residual, int ldr, void *out,
+                             int ldc, int M, int N, int K, float residual_scale, void *stream) {
+    return linear_rows16_rs_launch(x, ldx, W, ldw, bias, residual, ldr, out, ldc, M, N, K, residual_scale, (hipStream_t)stream);
 }
 
 #if LL_TUNING

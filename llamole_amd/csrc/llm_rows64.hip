@@ -28,7 +28,8 @@ typedef uint32_t r64_u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((ext_vector_type(8))) __bf16 r64_bf16x8;
 typedef __attribute__((ext_vector_type(4))) float r64_f32x4;
 
-enum { R64_PLAIN = 0, R64_RESIDUAL = 1, R64_SILU_MUL = 2 };
+// R64_RESIDUAL_SCALED (ll_linear_rows64_rs_bf16, Granite layout): bf16(residual + bf16(bf16(acc + bias) * rscale))
+enum { R64_PLAIN = 0, R64_RESIDUAL = 1, R64_SILU_MUL = 2, R64_RESIDUAL_SCALED = 3 };
 
 __device__ __forceinline__ float r64_bfr(float v) { return bf16_to_f32(f32_to_bf16(v)); }
 
@@ -62,12 +63,15 @@ __global__ __launch_bounds__(256) void rows64_pack_kernel(const bf16_t *__restri
 // prologue + drain of every workgroup cost 11 of 49 us on gate|up at 64 rows).
 // slab != nullptr: raw f32 partial sums [ksg][M][N] (no bias / epilogue).  tiles_n = padded weight tiles per matrix half (SILU_MUL: the up
 // tiles follow the gate tiles at +tiles_n).
-template <int EPI, int MB, int KS>
+// RS: empty, or one float = the multiplier of R64_RESIDUAL_SCALED (pack_scale, common.h) -- instantiated for the one-launch path: with
+// slabs the main kernel has no epilogue and the scaled arithmetic sits in the slab sum.
+template <int EPI, int MB, int KS, typename... RS>
 __global__ __launch_bounds__(512, KS == 256 ? 4 : 2) void rows64_kernel(const bf16_t *__restrict__ X, int ldx, const bf16_t *__restrict__ Wp,
                                                      const float *__restrict__ bias, const bf16_t *__restrict__ res, int ldr,
                                                      bf16_t *__restrict__ C, int ldc, float *__restrict__ slab,
                                                      const float *__restrict__ row_ssq, int ssq_chunks, float eps, int M, int N, int K,
-                                                     int tiles_n, int units, int ksg) {
+                                                     int tiles_n, int units, int ksg, RS... rscale) {
+    static_assert(sizeof...(RS) == (EPI == R64_RESIDUAL_SCALED ? 1 : 0), "the scale is an argument of the scaled epilogue alone");
     constexpr int R64_KS = KS, R64_XPITCH = KS * 2 + 16;
     constexpr int R64_KPW = KS / 32 / R64_KP;                   // k-steps per wave per stage (4 | 2)
     constexpr int R64_NW = R64_KPW * 2;                         // weight loads per wave per stage (two tiles)
@@ -231,6 +235,7 @@ __global__ __launch_bounds__(512, KS == 256 ? 4 : 2) void rows64_kernel(const bf
                     } else {
                         float v = sv[j] + ((bias && ok) ? bias[n] : 0.f);
                         if (EPI == R64_RESIDUAL) v = (ok ? bf16_to_f32(res[(int64_t)m * ldr + n]) : 0.f) + r64_bfr(v);
+                        if (EPI == R64_RESIDUAL_SCALED) v = (ok ? bf16_to_f32(res[(int64_t)m * ldr + n]) : 0.f) + r64_bfr(r64_bfr(v) * pack_scale(rscale...));
                         o[j] = f32_to_bf16(v);
                     }
                 }
@@ -283,12 +288,15 @@ __global__ __launch_bounds__(512, KS == 256 ? 4 : 2) void rows64_kernel(const bf
 // x the optional input row scale + bias[n]).  normw != nullptr: also XS[m][n] = bf16(out[m][n] * normw[n]) and ssq[m][chunk] = sum over the chunk of out[m][n]^2 (of the
 // ROUNDED output) -- the two halves of the next Linear's RMSNorm: the consumer multiplies its accumulator by rsqrt(sum(ssq) / N + eps).
 // splits == 0, C == nullptr: the pre-norm of the residual rows alone (the embedding rows ahead of the first layer).
-template <int EPI>
+// RS: empty, or one float = the multiplier of R64_RESIDUAL_SCALED.  XS and ssq are made from the rounded output row whatever the epilogue:
+// with the scaled residual they are the pre-norm of the scaled-residual result, as the next layer reads it.
+template <int EPI, typename... RS>
 __global__ __launch_bounds__(256) void rows64_reduce_kernel(const float *__restrict__ slab, int splits, const float *__restrict__ bias,
                                                             const bf16_t *__restrict__ res, int ldr, bf16_t *__restrict__ C, int ldc,
                                                             const bf16_t *__restrict__ normw, bf16_t *__restrict__ XS, int ldn,
                                                             float *__restrict__ ssq, const float *__restrict__ row_ssq, int ssq_chunks,
-                                                            float eps, int K, int M, int N) {
+                                                            float eps, int K, int M, int N, RS... rscale) {
+    static_assert(sizeof...(RS) == (EPI == R64_RESIDUAL_SCALED ? 1 : 0), "the scale is an argument of the scaled epilogue alone");
     __shared__ float red[4];
     const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int n = (blockIdx.y * 256 + tid) * 4;
@@ -322,6 +330,7 @@ __global__ __launch_bounds__(256) void rows64_reduce_kernel(const float *__restr
             if (n + j >= N) break;
             float r = v[j] + (bias ? bias[n + j] : 0.f);
             if (EPI == R64_RESIDUAL) r = bf16_to_f32(res[(int64_t)m * ldr + n + j]) + r64_bfr(r);
+            if (EPI == R64_RESIDUAL_SCALED) r = bf16_to_f32(res[(int64_t)m * ldr + n + j]) + r64_bfr(r64_bfr(r) * pack_scale(rscale...));
             const bf16_t ob = f32_to_bf16(r);
             if (C) C[(int64_t)m * ldc + n + j] = ob;
             r = bf16_to_f32(ob);
@@ -365,6 +374,22 @@ static int launch_rows64_ks(int ksg, hipStream_t s, const bf16_t *X, int ldx, co
     return LL_OK;
 }
 
+// the one-launch path of ll_linear_rows64_rs_bf16: the geometry of launch_rows64_ks at a plain / residual epilogue
+template <int MB>
+static int launch_rows64_rs(hipStream_t s, const bf16_t *X, int ldx, const bf16_t *Wp, const float *bias, const bf16_t *res, int ldr, bf16_t *C,
+                            int ldc, const float *row_ssq, int ssq_chunks, float eps, int M, int N, int K, float rscale) {
+    constexpr int KS = 512;
+    const size_t lds = (size_t)2 * MB * 16 * (KS * 2 + 16);
+    LL_TRY((allow_dynamic_lds<rows64_kernel<R64_RESIDUAL_SCALED, MB, KS, float>>(lds)));
+    const int tiles_n = (N + 15) / 16;
+    const int units = cdiv(tiles_n, 4);
+    const int slots = r64_cus();
+    const dim3 grid(units < slots ? units : slots);
+    hipLaunchKernelGGL((rows64_kernel<R64_RESIDUAL_SCALED, MB, KS, float>), grid, dim3(512), lds, s, X, ldx, Wp, bias, res, ldr, C, ldc,
+                       (float *)nullptr, row_ssq, ssq_chunks, eps, M, N, K, tiles_n, units, 1, rscale);
+    return LL_OK;
+}
+
 template <int EPI, int MB>
 static int launch_rows64_mb(int ksg, hipStream_t s, const bf16_t *X, int ldx, const bf16_t *Wp, const float *bias, const bf16_t *res, int ldr,
                             bf16_t *C, int ldc, float *slab, const float *row_ssq, int ssq_chunks, float eps, int M, int N, int K) {
@@ -379,21 +404,24 @@ static int launch_reduce(hipStream_t s, const float *slab, int ksg, const float 
     return LL_OK;
 }
 
-int linear_rows64_launch(const void *x, int ldx, const void *Wp, const float *bias, const void *residual, int ldr, void *out, int ldc, int M,
-                         int N, int K, int epi, const float *row_ssq, int ssq_chunks, float eps, const void *next_norm_w, void *scaled_out, int ldn,
-                         float *ssq_out, void *workspace, size_t workspace_bytes, hipStream_t s) {
-    LL_CHECK(x && Wp && out, "ll_linear_rows64_bf16: null argument");
-    LL_CHECK(M >= 1 && M <= 64, "ll_linear_rows64_bf16: M=%d rows (1..64)", M);
-    LL_CHECK(N >= 1 && K >= 32 && K % 32 == 0 && ldx % 8 == 0, "ll_linear_rows64_bf16: K must be a multiple of 32, ldx of 8");
-    LL_CHECK(epi >= R64_PLAIN && epi <= R64_SILU_MUL, "ll_linear_rows64_bf16: epilogue %d", epi);
-    LL_CHECK(epi != R64_RESIDUAL || residual, "ll_linear_rows64_bf16: residual epilogue without a residual");
-    LL_CHECK(epi != R64_SILU_MUL || N % 16 == 0, "ll_linear_rows64_bf16: SILU_MUL needs N %% 16 == 0 (N=%d)", N);
+// epi R64_RESIDUAL_SCALED (with rscale) is ll_linear_rows64_rs_bf16's; ll_linear_rows64_bf16 refuses it before it gets here
+static int linear_rows64_launch(const void *x, int ldx, const void *Wp, const float *bias, const void *residual, int ldr, void *out, int ldc, int M,
+                                int N, int K, int epi, const float *row_ssq, int ssq_chunks, float eps, const void *next_norm_w, void *scaled_out, int ldn,
+                                float *ssq_out, void *workspace, size_t workspace_bytes, hipStream_t s, float rscale = 1.f) {
+    const char *who = epi == R64_RESIDUAL_SCALED ? "ll_linear_rows64_rs_bf16" : "ll_linear_rows64_bf16";     // the entry the messages name
+    LL_CHECK(x && Wp && out, "%s: null argument", who);
+    LL_CHECK(M >= 1 && M <= 64, "%s: M=%d rows (1..64)", who, M);
+    LL_CHECK(N >= 1 && K >= 32 && K % 32 == 0 && ldx % 8 == 0, "%s: K must be a multiple of 32, ldx of 8", who);
+    LL_CHECK(epi >= R64_PLAIN && epi <= R64_RESIDUAL_SCALED, "%s: epilogue %d", who, epi);
+    LL_CHECK((epi != R64_RESIDUAL && epi != R64_RESIDUAL_SCALED) || residual, "%s: residual epilogue without a residual", who);
+    LL_CHECK(epi != R64_RESIDUAL_SCALED || scale_ok(rscale), "%s: residual_scale must be finite and non-zero", who);
+    LL_CHECK(epi != R64_SILU_MUL || N % 16 == 0, "%s: SILU_MUL needs N %% 16 == 0 (N=%d)", who, N);
     LL_CHECK(((uintptr_t)x & 15) == 0 && ((uintptr_t)Wp & 15) == 0 && (!workspace || ((uintptr_t)workspace & 15) == 0),
-             "ll_linear_rows64_bf16: operands must be 16-byte aligned");
-    LL_CHECK(!row_ssq || ssq_chunks >= 1, "ll_linear_rows64_bf16: row_ssq needs ssq_chunks >= 1");
+             "%s: operands must be 16-byte aligned", who);
+    LL_CHECK(!row_ssq || ssq_chunks >= 1, "%s: row_ssq needs ssq_chunks >= 1", who);
     const bool norm = next_norm_w != nullptr;
     LL_CHECK(!norm || (scaled_out && ssq_out && epi != R64_SILU_MUL && ldn >= N),
-             "ll_linear_rows64_bf16: the output pre-norm needs scaled_out, ssq_out and a plain / residual epilogue");
+             "%s: the output pre-norm needs scaled_out, ssq_out and a plain / residual epilogue", who);
     const bf16_t *X = (const bf16_t *)x, *W = (const bf16_t *)Wp, *rs = (const bf16_t *)residual;
     bf16_t *C = (bf16_t *)out;
     int ksg = 1;
@@ -411,7 +439,7 @@ int linear_rows64_launch(const void *x, int ldx, const void *Wp, const float *bi
     const size_t need = (size_t)ksg * M * N * 4;
     const bool two = ksg > 1 || norm;
     if (two && (!workspace || workspace_bytes < need)) {
-        LL_CHECK(!norm, "ll_linear_rows64_bf16: the output pre-norm needs %zu bytes of workspace", need);
+        LL_CHECK(!norm, "%s: the output pre-norm needs %zu bytes of workspace", who, need);
         ksg = 1;
     }
     float *slab = (ksg > 1 || norm) ? (float *)workspace : nullptr;
@@ -422,11 +450,17 @@ int linear_rows64_launch(const void *x, int ldx, const void *Wp, const float *bi
         else LL_TRY((launch_rows64_mb<EPI_, 4>(ksg, s, X, ldx, W, bias, rs, ldr, C, ldc, slab, slab ? nullptr : row_ssq, ssq_chunks, eps, M, N, K)));        \
     } while (0)
     if (epi == R64_PLAIN) LL_R64(R64_PLAIN);
-    else if (epi == R64_RESIDUAL) LL_R64(R64_RESIDUAL);
-    else LL_R64(R64_SILU_MUL);
+    else if (epi == R64_RESIDUAL || (epi == R64_RESIDUAL_SCALED && slab)) LL_R64(R64_RESIDUAL);     // with slabs the main kernel has no epilogue
+    else if (epi == R64_RESIDUAL_SCALED) {
+        if (mb == 2) LL_TRY((launch_rows64_rs<2>(s, X, ldx, W, bias, rs, ldr, C, ldc, row_ssq, ssq_chunks, eps, M, N, K, rscale)));
+        else LL_TRY((launch_rows64_rs<4>(s, X, ldx, W, bias, rs, ldr, C, ldc, row_ssq, ssq_chunks, eps, M, N, K, rscale)));
+    } else LL_R64(R64_SILU_MUL);
 #undef LL_R64
     if (slab) {
-        if (epi == R64_RESIDUAL)
+        if (epi == R64_RESIDUAL_SCALED) {
+            hipLaunchKernelGGL((rows64_reduce_kernel<R64_RESIDUAL_SCALED, float>), dim3(M, cdiv(N, 1024)), dim3(256), 0, s, slab, ksg, bias, rs, ldr, C, ldc,
+                               (const bf16_t *)next_norm_w, (bf16_t *)scaled_out, ldn, ssq_out, row_ssq, ssq_chunks, eps, K, M, N, rscale);
+        } else if (epi == R64_RESIDUAL)
             LL_TRY((launch_reduce<R64_RESIDUAL>(s, slab, ksg, bias, rs, ldr, C, ldc, (const bf16_t *)next_norm_w, (bf16_t *)scaled_out, ldn, ssq_out,
                                                 row_ssq, ssq_chunks, eps, K, M, N)));
         else
@@ -458,8 +492,17 @@ int ll_rows64_pack_bf16(const void *W, int ldw, int N, int K, void *packed, void
 int ll_linear_rows64_bf16(const void *x, int ldx, const void *Wp, const float *bias, const void *residual, int ldr, void *out, int ldc, int M,
                           int N, int K, int epi, const float *row_ssq, int ssq_chunks, float eps, const void *next_norm_w, void *scaled_out,
                           int ldn, float *ssq_out, void *workspace, int64_t workspace_bytes, void *stream) {
+    LL_CHECK(epi >= R64_PLAIN && epi <= R64_SILU_MUL, "ll_linear_rows64_bf16: epilogue %d", epi);
     return linear_rows64_launch(x, ldx, Wp, bias, residual, ldr, out, ldc, M, N, K, epi, row_ssq, ssq_chunks, eps, next_norm_w, scaled_out, ldn,
                                 ssq_out, workspace, workspace_bytes > 0 ? (size_t)workspace_bytes : 0, (hipStream_t)stream);
+}
+
+int ll_linear_rows64_rs_bf16(const void *x, int ldx, const void *Wp, const float *bias, const void *residual, int ldr, void *out, int ldc, int M,
+                             int N, int K, const float *row_ssq, int ssq_chunks, float eps, const void *next_norm_w, void *scaled_out, int ldn,
+                             float *ssq_out, void *workspace, int64_t workspace_bytes, float residual_scale, void *stream) {
+    return linear_rows64_launch(x, ldx, Wp, bias, residual, ldr, out, ldc, M, N, K, R64_RESIDUAL_SCALED, row_ssq, ssq_chunks, eps, next_norm_w,
+                                scaled_out, ldn, ssq_out, workspace, workspace_bytes > 0 ? (size_t)workspace_bytes : 0, (hipStream_t)stream,
+                                residual_scale);
 }
 
 int ll_rows64_ssq_chunks(int N) { return N >= 1 ? (N + 1023) / 1024 : 0; }

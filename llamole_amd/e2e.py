@@ -52,6 +52,17 @@ LLM_CONFIGS = {
                            num_experts=8, num_experts_per_tok=2, moe_intermediate_size=128, intermediate_size=512, vocab_size=2048,
                            max_position_embeddings=2048, rope_theta=10000.0, rms_norm_eps=1e-6, norm_topk_prob=True,
                            decoder_sparse_step=1, mlp_only_layers=[], tie_word_embeddings=False),
+    # Granite layout: the Llama layout plus four scalar multipliers (embedding, attention scale, both residual adds, logits).  The widths and
+    # multipliers of "granite-3.3-8b" are written from memory of the published ibm-granite/granite-3.3-8b-instruct config.json, not read from it;
+    # its published vocabulary (49159) is not a multiple of 8, which the HIP sampler and the lm_head GEMV need, so they fall back to torch there
+    "granite-3.3-8b": dict(cls="Granite", hidden_size=4096, num_hidden_layers=40, num_attention_heads=32, num_key_value_heads=8,
+                           intermediate_size=12800, vocab_size=49159, max_position_embeddings=131072, rope_theta=10000000.0,
+                           rms_norm_eps=1e-5, tie_word_embeddings=True, embedding_multiplier=12.0, attention_multiplier=0.0078125,
+                           residual_multiplier=0.22, logits_scaling=16.0),
+    "tiny-granite": dict(cls="Granite", hidden_size=256, num_hidden_layers=2, num_attention_heads=4, num_key_value_heads=2,
+                         intermediate_size=512, vocab_size=2048, max_position_embeddings=2048, rope_theta=10000.0,
+                         rms_norm_eps=1e-5, tie_word_embeddings=False, embedding_multiplier=12.0, attention_multiplier=0.0078125,
+                         residual_multiplier=0.22, logits_scaling=8.0),
 }
 
 # rope_parameters of the published meta-llama/Meta-Llama-3.1-8B-Instruct config.json (rope_scaling there): the "llama-3.1-8b" entry above has the

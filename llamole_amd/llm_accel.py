@@ -117,11 +117,12 @@ class _PackedWQ:
         return True
 
 
-def _rows64(lib, x2, ldx, wp: "_Packed64", bias, res, N, epi, row_ssq=None, eps=0.0, next_norm=None):
+def _rows64(lib, x2, ldx, wp: "_Packed64", bias, res, N, epi, row_ssq=None, eps=0.0, next_norm=None, rscale=None):
     """17..64 token rows through ll_linear_rows64_bf16 on a packed weight; matrices with few 64-row groups (o_proj, down_proj) get scratch
     for the cross-workgroup K split (f32 slabs summed in slice order by a second launch on the same stream).
     ``row_ssq`` [M, chunks] f32: x2 is a pre-scaled row bf16(h * w_norm) and the accumulator is multiplied by rsqrt(mean(h^2) + eps).
-    ``next_norm``: also return (bf16(out * next_norm), per-chunk sums of out^2) -- the two halves of the NEXT Linear's RMSNorm."""
+    ``next_norm``: also return (bf16(out * next_norm), per-chunk sums of out^2) -- the two halves of the NEXT Linear's RMSNorm.
+    ``rscale`` (residual epilogue only): the layer's residual_multiplier -- the call goes to ll_linear_rows64_rs_bf16."""
     M, K = x2.shape[0], wp.K
     out = torch.empty(M, N, dtype=torch.bfloat16, device=x2.device)
     xs = ssq = None
@@ -132,15 +133,20 @@ def _rows64(lib, x2, ldx, wp: "_Packed64", bias, res, N, epi, row_ssq=None, eps=
     if epi != 2 and (next_norm is not None or N < 192 * 64):
         wsb = int(lib.ll_linear_rows64_workspace_bytes(M, N))
         ws = torch.empty(wsb, dtype=torch.uint8, device=x2.device)
-    rc = lib.ll_linear_rows64_bf16(x2.data_ptr(), ldx, wp.t.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                   res.data_ptr() if res is not None else None, res.stride(0) if res is not None else 0,
-                                   out.data_ptr(), N, M, N, K, epi, row_ssq.data_ptr() if row_ssq is not None else None,
-                                   row_ssq.shape[1] if row_ssq is not None else 0, eps,
-                                   next_norm.data_ptr() if next_norm is not None else None, xs.data_ptr() if xs is not None else None, N,
-                                   ssq.data_ptr() if ssq is not None else None, ws.data_ptr() if ws is not None else None, wsb,
-                                   torch.cuda.current_stream().cuda_stream)
+    head = (x2.data_ptr(), ldx, wp.t.data_ptr(), bias.data_ptr() if bias is not None else None,
+            res.data_ptr() if res is not None else None, res.stride(0) if res is not None else 0, out.data_ptr(), N, M, N, K)
+    tail = (row_ssq.data_ptr() if row_ssq is not None else None, row_ssq.shape[1] if row_ssq is not None else 0, eps,
+            next_norm.data_ptr() if next_norm is not None else None, xs.data_ptr() if xs is not None else None, N,
+            ssq.data_ptr() if ssq is not None else None, ws.data_ptr() if ws is not None else None, wsb)
+    if rscale is not None:
+        assert epi == 1, "the scaled residual epilogue stands in for the residual epilogue only"
+        name = "ll_linear_rows64_rs_bf16"
+        rc = lib.ll_linear_rows64_rs_bf16(*head, *tail, rscale, torch.cuda.current_stream().cuda_stream)
+    else:
+        name = "ll_linear_rows64_bf16"
+        rc = lib.ll_linear_rows64_bf16(*head, epi, *tail, torch.cuda.current_stream().cuda_stream)
     if rc != 0:
-        _lib.check(rc, "ll_linear_rows64_bf16")
+        _lib.check(rc, name)
     return out if next_norm is None else (out, xs, ssq)
 
 
@@ -621,6 +627,43 @@ def _kv_layer_ok(cl) -> bool:
     return cl.keys.dtype == torch.bfloat16
 
 
+# ------------------------------------------------------------------------------------------ Granite layout: scalar multipliers
+def hf_scaled_residual(residual: torch.Tensor, y: torch.Tensor, m: float) -> torch.Tensor:
+    """GraniteDecoderLayer.forward's ``residual + hidden_states * self.residual_multiplier`` stated in torch as the kernels compute it (the
+    LL_GEMV_RESIDUAL_SCALED contract of include/llamole_hip.h): y is the Linear's bf16 output, the product is taken in f32 with the multiplier
+    rounded to f32 and rounded to bf16, then the sum is.  On bf16 tensors this is bit for bit what HF's line gives."""
+    m32 = torch.tensor(float(m), dtype=torch.float32, device=y.device)
+    scaled = (y.to(torch.bfloat16).float() * m32).to(torch.bfloat16)
+    return (residual.to(torch.bfloat16).float() + scaled.float()).to(torch.bfloat16)
+
+
+def hf_scaled_embedding(table: torch.Tensor, ids: torch.Tensor, m: float) -> torch.Tensor:
+    """GraniteModel.forward's ``embed_tokens(input_ids) * self.embedding_multiplier`` as ll_embed_rows_bf16 computes it: f32 product with
+    the multiplier rounded to f32, one rounding to bf16."""
+    m32 = torch.tensor(float(m), dtype=torch.float32, device=table.device)
+    return (table[ids].float() * m32).to(torch.bfloat16)
+
+
+def _multiplier(owner, name: str):
+    """(value as a float or None when it is not a number, whether it is a finite non-zero number) of a scalar multiplier attribute; an
+    absent attribute is 1.0."""
+    import math
+    v = getattr(owner, name, 1.0)
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        return None, False
+    return f, (math.isfinite(f) and f != 0.0 and abs(f) <= 3.0e38 and float(torch.tensor(f, dtype=torch.float32)) != 0.0)
+
+
+RESIDUAL_MULTIPLIER_DECLINED = "residual_multiplier is not a finite non-zero number"
+MOE_RESIDUAL_MULTIPLIER_DECLINED = "MoE layer with a residual_multiplier (the slot-sum launch has no scaled residual)"
+EMBEDDING_MULTIPLIER_DECLINED = "embedding_multiplier is not a finite non-zero number"
+EMBEDDING_TABLE_DECLINED = "embedding_multiplier with an embedding table that is not a contiguous bf16 matrix of a width that is a multiple of 8"
+WQ_RESIDUAL_MULTIPLIER_REASON = ("residual_multiplier: the packed-code kernels have no scaled residual epilogue; these layers run the bf16 "
+                                 "kernels on their dequantised weights")
+
+
 # ------------------------------------------------------------------------------------------ whole decoder layer = 5 launches
 class _FusedLayer:
     """Decode-step state of one HF decoder layer (Qwen2 / Llama / Mistral layout): concatenated q|k|v and gate|up weights
@@ -646,6 +689,9 @@ class _FusedLayer:
         self.nh, self.nkv = self.nq // self.D, self.nkv_dim // self.D
         self.H = q.in_features
         self.scaling = float(att.scaling)
+        # Granite layout: both residual adds are residual + y * residual_multiplier; None = the plain residual epilogue (absent or 1.0)
+        rm = _multiplier(layer, "residual_multiplier")[0]
+        self.rscale = None if rm == 1.0 else rm
         # Qwen3 layout: an RMSNorm over head_dim on every q and k head row in front of the rotation, done inside the attention launch; the
         # modules stay the owners of the weights (read at every call: no copy to keep in step)
         self.qn, self.kn = getattr(att, "q_norm", None), getattr(att, "k_norm", None)
@@ -663,7 +709,8 @@ class _FusedLayer:
         self.wq_bits = bits.pop() if len(bits) == 1 else None
         self.pq = None
         self.use_wq = True      # off: the bf16 kernels on the dequantised weights (tests, A/B timing)
-        if self.wq_bits is not None and self.stream_ok and self.wq_ok:
+        # (a layer with a residual_multiplier keeps no codes: the packed-code kernels have no scaled residual epilogue)
+        if self.wq_bits is not None and self.stream_ok and self.wq_ok and self.rscale is None:
             self.pq = tuple(_PackedWQ(lib, w, self.wq_bits, key) for w, key in zip(self._srcs(), self._keys64()))
 
     def _init_mlp(self, layer, attn_mods):
@@ -734,8 +781,21 @@ class _FusedLayer:
             _lib.check(rc, name)
         return out
 
+    def _gemv_rs(self, x, w, bias, res, N, K):
+        """o_proj / down_proj + the scaled residual add of a Granite layer on 1..16 rows: the ``_gemv`` choice of kernel, the *_rs entries."""
+        M = x.shape[0]
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+        name = "ll_linear_rows16_rs_bf16" if M > FMA_GEMV_ROWS and self.stream_ok else "ll_gemv_fused_rs_bf16"
+        rc = getattr(self.lib, name)(x.data_ptr(), x.stride(0), w.data_ptr(), K, bias.data_ptr() if bias is not None else None, res.data_ptr(),
+                                     res.stride(0), out.data_ptr(), N, M, N, K, self.rscale, torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            _lib.check(rc, name)
+        return out
+
     def _gemv(self, x, w, bias, norm_w, eps, res, N, K, epi, pk=None, which=None):
         M = x.shape[0]
+        if epi == 1 and self.rscale is not None:
+            return self._gemv_rs(x, w, bias, res, N, K)
         if pk is not None and self.use_wq and FMA_GEMV_ROWS == 2 and M in WQ_ROUTES.get((pk.bits, which), ()):
             return self._gemv_wq(x, pk, bias, norm_w, eps, res, N, K, epi)
         out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
@@ -823,11 +883,11 @@ class _FusedLayer:
         nqkv = self.nq + 2 * self.nkv_dim
         qkv = _rows64(self.lib, xs, xs.stride(0), pqkv, self.bqkv, None, nqkv, 0, row_ssq=ssq, eps=self.eps1)
         att = self._attn(qkv, nqkv, mask, cache, pe, B, h.device)
-        h1, xs2, ssq2 = _rows64(self.lib, att, att.stride(0), po, self.bo, x, H, 1, next_norm=self.n2.weight)
+        h1, xs2, ssq2 = _rows64(self.lib, att, att.stride(0), po, self.bo, x, H, 1, next_norm=self.n2.weight, rscale=self.rscale)
         act = _rows64(self.lib, xs2, xs2.stride(0), pgu, None, None, self.I, 2, row_ssq=ssq2, eps=self.eps2)
         if next_norm is None:
-            return _rows64(self.lib, act, act.stride(0), pdown, None, h1, H, 1).view(B, 1, H), None
-        h2, xs3, ssq3 = _rows64(self.lib, act, act.stride(0), pdown, None, h1, H, 1, next_norm=next_norm)
+            return _rows64(self.lib, act, act.stride(0), pdown, None, h1, H, 1, rscale=self.rscale).view(B, 1, H), None
+        h2, xs3, ssq3 = _rows64(self.lib, act, act.stride(0), pdown, None, h1, H, 1, next_norm=next_norm, rscale=self.rscale)
         return h2.view(B, 1, H), (xs3, ssq3)
 
     def run(self, h, mask, cache, pe):
@@ -1090,6 +1150,11 @@ def decoder_layer_declined(layer: nn.Module) -> Optional[str]:
     why = _head_norm_declined(att)
     if why is not None:
         return why
+    rm, rm_ok = _multiplier(layer, "residual_multiplier")
+    if not rm_ok:
+        return RESIDUAL_MULTIPLIER_DECLINED
+    if moe and rm != 1.0:
+        return MOE_RESIDUAL_MULTIPLIER_DECLINED
     norms = [m for m in (getattr(att, "q_norm", None), getattr(att, "k_norm", None)) if m is not None]
     extra = [m.weight for m in norms] + ([mlp.experts.gate_up_proj, mlp.experts.down_proj, mlp.gate.weight] if moe else [])
     if att.q_proj.weight.dtype != torch.bfloat16 or any(t.dtype != torch.bfloat16 for t in extra):
@@ -1147,6 +1212,7 @@ def _model_forward(self, input_ids=None, attention_mask=None, position_ids=None,
     layers = self.layers[: self.config.num_hidden_layers]
     if (input_ids is not None and inputs_embeds is None and input_ids.dim() == 2 and input_ids.shape[1] == 1
             and input_ids.shape[0] <= MAX_STREAM_ROWS and input_ids.is_cuda and not torch.is_grad_enabled() and past_key_values is not None
+            and (st.get("embed_scale") is None or input_ids.dtype == torch.long)      # ll_embed_rows_bf16 reads int64 ids
             and attention_mask is not None and attention_mask.dim() == 2 and attention_mask.dtype == torch.long
             and attention_mask.stride(1) == 1 and position_ids is not None and position_ids.shape == input_ids.shape
             and position_ids.dtype == torch.long and not kwargs.get("output_hidden_states") and not kwargs.get("output_attentions")
@@ -1156,7 +1222,7 @@ def _model_forward(self, input_ids=None, attention_mask=None, position_ids=None,
             and layers[0]._ll_fused.attn_serves(input_ids.shape[0], 1, attention_mask.shape[1], _is_kv8(past_key_values.layers[0]))):
         B, maxlen, D = input_ids.shape[0], attention_mask.shape[1], st["D"]
         dev = input_ids.device
-        h = self.embed_tokens(input_ids)
+        h = _embed(self, st, input_ids)
         if h.dtype == torch.bfloat16 and h.is_contiguous():
             cos = torch.empty(B, 1, D, dtype=torch.bfloat16, device=dev)
             sin = torch.empty(B, 1, D, dtype=torch.bfloat16, device=dev)
@@ -1209,6 +1275,24 @@ def _model_forward(self, input_ids=None, attention_mask=None, position_ids=None,
                                past_key_values=past_key_values, inputs_embeds=inputs_embeds, use_cache=use_cache, **kwargs)
 
 
+def _embed(self, st, input_ids):
+    """The input rows of the layers: ``embed_tokens(input_ids)``, or for a model with an embedding_multiplier (Granite layout) the gather
+    and the scale in one launch (ll_embed_rows_bf16) -- [B, S, H] bf16 either way."""
+    m = st.get("embed_scale")
+    if m is None:
+        return self.embed_tokens(input_ids)
+    table = self.embed_tokens.weight
+    V, H = table.shape
+    assert input_ids.dtype == torch.long, "ll_embed_rows_bf16 reads int64 ids (the callers send other dtypes to HF's forward)"
+    ids = input_ids.contiguous()
+    out = torch.empty(*ids.shape, H, dtype=torch.bfloat16, device=ids.device)
+    rc = st["lib"].ll_embed_rows_bf16(ids.data_ptr(), table.data_ptr(), table.stride(0), out.data_ptr(), H, ids.numel(), V, H, m,
+                                      torch.cuda.current_stream().cuda_stream)
+    if rc != 0:
+        _lib.check(rc, "ll_embed_rows_bf16")
+    return out
+
+
 def _suffix_forward(self, st, layers, input_ids, attention_mask, position_ids, cache, use_cache, kwargs):
     """[B,S] new tokens (3 <= B*S <= 16) appended at the cache position held by layer 0's counter -- GraphedDecoder.continue_hidden, the
     reference's query-token re-forward -- on the five-launch layers: one prologue launch (cos/sin per row, key mask per row: slot
@@ -1218,6 +1302,7 @@ def _suffix_forward(self, st, layers, input_ids, attention_mask, position_ids, c
     R = B * S
     clayers = getattr(cache, "layers", None)
     if not (S >= 2 and FMA_GEMV_ROWS < R <= MAX_ROWS16 and input_ids.is_cuda and not torch.is_grad_enabled() and clayers
+            and (st.get("embed_scale") is None or input_ids.dtype == torch.long)      # ll_embed_rows_bf16 reads int64 ids
             and all(getattr(l, "_ll_fused_update", False) for l in clayers) and attention_mask is not None and attention_mask.dim() == 2
             and attention_mask.dtype == torch.long and attention_mask.stride(1) == 1 and attention_mask.shape[0] == B
             and attention_mask.shape[1] == clayers[0].keys.shape[2] and _kv_layer_ok(clayers[0])
@@ -1227,7 +1312,7 @@ def _suffix_forward(self, st, layers, input_ids, attention_mask, position_ids, c
             and all(l._ll_fused.stream_ok for l in layers)
             and layers[0]._ll_fused.attn_serves(B, S, attention_mask.shape[1], _is_kv8(clayers[0]))):
         return None
-    h = self.embed_tokens(input_ids)
+    h = _embed(self, st, input_ids)
     if h.dtype != torch.bfloat16 or not h.is_contiguous():
         return None
     maxlen, D, dev = attention_mask.shape[1], st["D"], input_ids.device
@@ -1307,6 +1392,14 @@ def model_decode_declined(model: nn.Module) -> Optional[str]:
         if (inv0 is None or inv0.dtype != torch.float32 or not inv0.is_cuda or inv0.shape != rot.inv_freq.shape
                 or not getattr(getattr(rot, "config", None), "max_position_embeddings", None)):
             return "dynamic rope without an f32 device original_inv_freq"
+    em, em_ok = _multiplier(base, "embedding_multiplier")
+    if not em_ok:
+        return EMBEDDING_MULTIPLIER_DECLINED
+    if em != 1.0:
+        w = getattr(base.embed_tokens, "weight", None)
+        if not (type(base.embed_tokens) is nn.Embedding and w is not None and w.dtype == torch.bfloat16 and w.dim() == 2 and w.is_contiguous()
+                and w.shape[1] % 8 == 0):
+            return EMBEDDING_TABLE_DECLINED
     return None
 
 
@@ -1323,6 +1416,9 @@ def fuse_model_decode(model: nn.Module) -> bool:
     # the output class of the base model's own forward: a MoE model's causal-LM head reads `router_logits` (None here) off it
     out_cls = getattr(sys.modules.get(type(base).__module__), "MoeModelOutputWithPast", BaseModelOutputWithPast)
     base._ll_decode = {"lib": _lib.load(), "D": base.layers[0]._ll_fused.D, "out_cls": out_cls}
+    em = _multiplier(base, "embedding_multiplier")[0]
+    if em != 1.0:
+        base._ll_decode["embed_scale"] = em         # Granite layout: gather and scale in one launch (_embed)
     if rot.rope_type == "dynamic":
         base._ll_decode["dyn"] = {"max_pos": int(rot.config.max_position_embeddings), "tables": {}}
     base._ll_model_orig = base.forward
@@ -1402,4 +1498,6 @@ def accelerate_llm(model: nn.Module, linears: bool = True, fuse: bool = True, la
         q["packed_routes"] = {m: (sorted(WQ_ROUTES.get((bits, m), ())) if FMA_GEMV_ROWS == 2 else []) for m in WQ_MATRICES}
         if any(_is_moe_block(getattr(l, "mlp", None)) for l in (getattr(base, "layers", None) or [])):
             q["experts"] = "bf16"       # expert and router weights are neither rounded nor packed: only the attention Linears of a MoE layer are
+        if any(st is not None and st.rscale is not None and st.wq_bits is not None for st in fused):
+            q["bf16_reason"] = WQ_RESIDUAL_MULTIPLIER_REASON
     return info
