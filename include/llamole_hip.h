@@ -484,6 +484,34 @@ int ll_sample_token_penalty_bf16(const void *logits, int64_t ld, int B, int V, f
                                  int64_t *out_tokens, int64_t ld_out, int max_new, int64_t *step, int64_t *posid, int64_t *pos, int advance,
                                  void *seen, int64_t seen_bytes, int cap, float penalty, void *stream);
 
+/* Prompt-lookup speculative decoding of ONE sequence (HF generate(prompt_lookup_num_tokens = k, max_matching_ngram_size = n);
+ * llamole_amd/llm_spec.py states the step in torch).  State, all on the device: the sampler's done / tok / out_tokens / step / posid / pos of
+ * row 0, a history hist[0, *hist_len) of int64 tokens (capacity hist_cap: the call's input_ids row, then every emitted token) and the S = k + 1
+ * static input rows of the captured forward, ids / position_ids / cache_position.
+ * Drafting rule (PromptLookupCandidateGenerator.get_candidates): ngram sizes min(n, len - 1) down to 1; the leftmost earlier occurrence of
+ *     the history's last ngram that has a non-empty continuation; the drafts d_1.. are the up to k tokens behind it.  ids[0] = *tok (the
+ *     last emitted token), ids[i] = d_i, rows without a draft repeat *tok; position_ids[i] = *posid + i; cache_position[i] = *pos + i.
+ * ll_spec_draft : one launch of one workgroup.  append != 0: *tok is first appended to the history (the token sampled from the prefill
+ *     logits).  2 <= k <= 15, n >= 1, hist_cap >= 1; a full history is not appended to.
+ * ll_spec_verify_bf16 : two launches, no host sync.  logits bf16 [S, V] of the rows ids[0..S) (row stride ld; 3 <= S <= 16, V % 8 == 0,
+ *     V <= 163840, ld % 8 == 0, 16-byte aligned).  (1) Row i is sampled by the device code of ll_sample_token_topk_bf16 exactly as that
+ *     samples row b = 0 at step value t + i, t = *step: same sanitising, temperature, top-k, top-p, Philox4x32-10 counter (t + i, 0) under
+ *     *seed (greedy != 0: argmax, lowest index on ties) -> x_i (xs, [S] scratch).  (2) a = the number of leading i < k with
+ *     x_i == ids[i + 1]; x_0..x_a are emitted, cut after the first token of eos[0..n_eos) (*done = 1) and at min(*max_new, out_cap) tokens
+ *     in all; e = the number emitted.  out_tokens[t .. t + e) and the history receive them; *step += e, *posid += e, *pos += e,
+ *     *cumulative_length = the new *pos (NULL: skipped; layer 0's counter of a fused cache), *tok = the last one emitted;
+ *     stats[0] += 1 (forwards), stats[1] += e - 1 (accepted drafts).  With draft_next != 0 the second launch ends by writing the next
+ *     step's ids / position_ids / cache_position by the rule above.  A call with *done set or *step >= min(*max_new, out_cap) writes
+ *     nothing but xs.
+ * Bounds violations: LL_EINVAL, nothing is launched, nothing is written. */
+int ll_spec_draft(int64_t *hist, int hist_cap, int64_t *hist_len, const int64_t *tok, int append, int k, int n, const int64_t *pos,
+                  const int64_t *posid, int64_t *ids, int64_t *position_ids, int64_t *cache_position, void *stream);
+int ll_spec_verify_bf16(const void *logits, int64_t ld, int S, int V, float inv_temp, float top_p, int top_k, int greedy, const int64_t *seed,
+                        const int64_t *eos, int n_eos, void *done, int64_t *tok, int64_t *out_tokens, int out_cap, const int64_t *max_new,
+                        int64_t *step, int64_t *posid, int64_t *pos, int64_t *cumulative_length, int64_t *ids, int64_t *position_ids,
+                        int64_t *cache_position, int64_t *hist, int hist_cap, int64_t *hist_len, int n, int draft_next, int64_t *stats,
+                        int64_t *xs, void *stream);
+
 /* Beam search of the graphed decode (HF GenerationMixin._beam_search; llamole_amd/llm_beam.py states the same step in torch and the
  * layout of its state): B items of nb beams, rows r = b * nb + j.
  * ll_beam_state_bytes(B, nb, K, T): bytes of the state (int32 / f32 segments: running scores, hypotheses, flags, parents, per-step

@@ -115,6 +115,9 @@ SIGNATURES = {
     "ll_seen_set_init": (_I, [_P, _I64, _I, _I, _I, _P, _I64, _I, _P]),
     "ll_sample_token_penalty_bf16": (_I, [_P, _I64, _I, _I, _F, _F, _I, _I, _P, _P, _I, _I64, _P, _P, _P, _I64, _I, _P, _P, _P, _I,
                                           _P, _I64, _I, _F, _P]),
+    "ll_spec_draft": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "ll_spec_verify_bf16": (_I, [_P, _I64, _I, _I, _F, _F, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I,
+                                 _I, _P, _P, _P]),
     "ll_beam_state_bytes": (_I64, [_I, _I, _I, _I]),
     "ll_beam_step_bf16": (_I, [_P, _I64, _I, _I, _I, _I, _I, _P, _I64, _P, _I, _I, _F, _I, _I, _F, _I, _F, _P, _P, _P, _P, _I, _P]),
     "ll_beam_kv_reorder_bf16": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P]),

@@ -256,4 +256,9 @@ void set_panel_gemm(bool on);
 int linear_rows16_launch(const void *x, int ldx, const void *W, int ldw, const float *bias, const void *norm_w, float eps,
                          const void *residual, int ldr, void *out, int ldc, int M, int N, int K, int epi, int out_f32, hipStream_t stream);
 
+// the one-workgroup token sampler on S rows of one sequence's logits, row i drawn as row 0 at step value step[0] + i (llm_sample.hip; the
+// caller, ll_spec_verify_bf16 in llm_spec.hip, checks the bounds): xs[i] = the token, nothing else is written
+int sample_rows_spec(const void *logits, int64_t ld, int S, int V, float inv_temp, float top_p, int top_k, int greedy, const int64_t *seed,
+                     const int64_t *step, int64_t *xs, hipStream_t stream);
+
 }  // namespace ll

@@ -47,6 +47,7 @@ struct SampleArgs {
     unsigned long long *dbg;   // optional [B,4]: Z, kept mass, boundary key, sampled key
     unsigned int *cand_total;  // optional [B,4]: row header of sample_candidates_kernel -- count, largest key, 0xffff - smallest key (reset to 0 here)
     const uint2 *cand;         // [B, SAMPLE_CAND_CAP] (key, token index)
+    long long *spec_x;         // SPEC instantiation only (sample_rows_spec): [gridDim.x] the sampled tokens; nothing else is written
 };
 
 __device__ __forceinline__ uint32_t key_of(uint32_t x) {   // x: raw bf16 bits (16 low bits), NaN -> 0, inf -> +-max
@@ -201,6 +202,9 @@ struct SampleLds {
 
 // Steps 3 and 4 on the histogram L.cnt[0 .. kmax - klo]: top-k cut, nucleus boundary, one Philox draw -> the sampled VALUE k2 and the rank
 // of the token among those sharing it.  Expects a barrier behind the last histogram update.
+// SPEC (the speculative verify, llm_spec.hip): workgroup b samples logits row b as ROW 0 of a one-sequence decode would at step value
+// step[0] + b, i.e. under the Philox counter (step[0] + b, 0).
+template <bool SPEC = false>
 __device__ __forceinline__ void nucleus_scan(SampleLds &L, const SampleArgs &a, int b, int tid, int lane, int wave, uint32_t kmax,
                                              uint32_t klo, float m, uint32_t &k2, uint32_t &rank) {
     // ---- 3. thread t owns d in [bpt t, bpt t + bpt), descending values: masses = count * 2^-40 fixed-point exp.  All 36 bins per
@@ -302,8 +306,8 @@ __device__ __forceinline__ void nucleus_scan(SampleLds &L, const SampleArgs &a, 
         unsigned long long M = A;    // kept mass: everything down to and including the boundary value
         if (a.top_p >= 1.f && dk == 0xffffffffu) M = Z;   // tail included when nothing is filtered
         const unsigned long long sd = (unsigned long long)*a.seed;
-        const unsigned long long st = (unsigned long long)a.step[b];
-        const uint4 rnd = philox4x32(make_uint4((uint32_t)st, (uint32_t)(st >> 32), (uint32_t)b, 0x5A17u),
+        const unsigned long long st = (unsigned long long)(SPEC ? a.step[0] + b : a.step[b]);
+        const uint4 rnd = philox4x32(make_uint4((uint32_t)st, (uint32_t)(st >> 32), (uint32_t)(SPEC ? 0 : b), 0x5A17u),
                                      make_uint2((uint32_t)sd, (uint32_t)(sd >> 32)));
         const unsigned long long r64 = ((unsigned long long)rnd.x << 32) | rnd.y;
         L.R = __umul64hi(r64, M);
@@ -613,11 +617,13 @@ __device__ __forceinline__ void sample_pick(SampleLds &L, const SampleArgs &a, u
     }
 }
 
-template <int CH>
+template <int CH, bool SPEC = false>
 __global__ __launch_bounds__(1024) void sample_token_kernel(SampleArgs a) {
     __shared__ SampleLds L;
-    sample_prefetch(L, a, blockIdx.x, threadIdx.x);
-    if (a.cand_total && sample_fast<CH>(L, a, blockIdx.x, threadIdx.x, threadIdx.x & 63, threadIdx.x >> 6)) return;
+    if constexpr (!SPEC) {
+        sample_prefetch(L, a, blockIdx.x, threadIdx.x);
+        if (a.cand_total && sample_fast<CH>(L, a, blockIdx.x, threadIdx.x, threadIdx.x & 63, threadIdx.x >> 6)) return;
+    }
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bf16_t *row = a.logits + (int64_t)b * a.ld;
     const int nchunk = a.V / 8;
@@ -640,10 +646,15 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(SampleArgs a) {
         const uint32_t klo = sample_klo(L, a, tid, lane, wave, kmax, kmaxi);
         sample_hist<CH>(L, a, w, kmax, klo, m);
         __syncthreads();
-        nucleus_scan(L, a, b, tid, lane, wave, kmax, klo, m, k2, rank);
+        nucleus_scan<SPEC>(L, a, b, tid, lane, wave, kmax, klo, m, k2, rank);
     }
     sample_pick<CH>(L, a, w, tid, lane, wave, k2, rank);
-    sample_finish(L, a, b, tid);
+    if constexpr (SPEC) {
+        __syncthreads();
+        if (tid == 0) a.spec_x[b] = (long long)L.tok;      // the accept kernel does the bookkeeping of all rows at once
+    } else {
+        sample_finish(L, a, b, tid);
+    }
 }
 
 
@@ -1034,7 +1045,7 @@ extern "C" int ll_sample_token_topk_ws_bf16(const void *logits, int64_t ld, int 
     a.done = (unsigned char *)done; a.tok = (long long *)tok; a.out_tokens = (long long *)out_tokens; a.ld_out = ld_out;
     a.max_new = max_new; a.step = (long long *)step; a.posid = (long long *)posid; a.pos = (long long *)pos;
     a.advance = advance; a.dbg = (unsigned long long *)dbg;
-    a.cand_total = nullptr; a.cand = nullptr;
+    a.cand_total = nullptr; a.cand = nullptr; a.spec_x = nullptr;
     hipStream_t s = (hipStream_t)stream;
     // sampling a few rows with top-k of at most 128 and a workspace: many workgroups pick the row's candidates, one workgroup per row finishes on them
     // (the same token as the one-workgroup path, which still takes over when a row has more than 16384 candidates)
@@ -1050,6 +1061,23 @@ extern "C" int ll_sample_token_topk_ws_bf16(const void *logits, int64_t ld, int 
     else if (per <= 16) hipLaunchKernelGGL((sample_token_kernel<16>), dim3(B), dim3(1024), 0, s, a);
     else if (per <= 19) hipLaunchKernelGGL((sample_token_kernel<19>), dim3(B), dim3(1024), 0, s, a);     // 152 064 (Qwen2): 76 key registers
     else hipLaunchKernelGGL((sample_token_kernel<20>), dim3(B), dim3(1024), 0, s, a);
+    LL_LAUNCH_CHECK();
+    return LL_OK;
+}
+
+// The sampling half of ll_spec_verify_bf16 (llm_spec.hip, which has checked the bounds): S workgroups of the one-workgroup sampler, row i
+// of the logits drawn as ll_sample_token_topk_bf16 draws row 0 at step value step[0] + i; xs[i] = the token, nothing else is written.
+int ll::sample_rows_spec(const void *logits, int64_t ld, int S, int V, float inv_temp, float top_p, int top_k, int greedy, const int64_t *seed,
+                         const int64_t *step, int64_t *xs, hipStream_t s) {
+    SampleArgs a = {};
+    a.logits = (const bf16_t *)logits; a.ld = ld; a.V = V; a.inv_temp = inv_temp; a.top_p = top_p; a.top_k = top_k < 0 ? 0 : top_k; a.greedy = greedy;
+    a.seed = (const long long *)seed; a.step = (long long *)step; a.spec_x = (long long *)xs;
+    const int per = cdiv(V, 8 * 1024);
+    if (per <= 2) hipLaunchKernelGGL((sample_token_kernel<2, true>), dim3(S), dim3(1024), 0, s, a);
+    else if (per <= 8) hipLaunchKernelGGL((sample_token_kernel<8, true>), dim3(S), dim3(1024), 0, s, a);
+    else if (per <= 16) hipLaunchKernelGGL((sample_token_kernel<16, true>), dim3(S), dim3(1024), 0, s, a);
+    else if (per <= 19) hipLaunchKernelGGL((sample_token_kernel<19, true>), dim3(S), dim3(1024), 0, s, a);
+    else hipLaunchKernelGGL((sample_token_kernel<20, true>), dim3(S), dim3(1024), 0, s, a);
     LL_LAUNCH_CHECK();
     return LL_OK;
 }
@@ -1085,7 +1113,7 @@ extern "C" int ll_sample_token_penalty_bf16(const void *logits, int64_t ld, int 
     a.done = (unsigned char *)done; a.tok = (long long *)tok; a.out_tokens = (long long *)out_tokens; a.ld_out = ld_out;
     a.max_new = max_new; a.step = (long long *)step; a.posid = (long long *)posid; a.pos = (long long *)pos;
     a.advance = advance; a.dbg = nullptr;
-    a.cand_total = nullptr; a.cand = nullptr;           // no split path: its candidates are picked on raw keys
+    a.cand_total = nullptr; a.cand = nullptr; a.spec_x = nullptr;           // no split path: its candidates are picked on raw keys
     pa.seen = (unsigned char *)seen; pa.rb = seen_row_bytes(V, cap); pa.cap = cap; pa.pen = penalty; pa.pen_on = penalty != 1.f;
     hipStream_t s = (hipStream_t)stream;
     const int per = cdiv(V, 8 * 1024);

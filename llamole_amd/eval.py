@@ -70,6 +70,10 @@ def load_yaml_args(path: str, overrides: Optional[Dict[str, Any]] = None):
     gen = {"do_sample": cfg.get("do_sample", True), "temperature": cfg.get("temperature", 0.95), "top_p": cfg.get("top_p", 0.7),
            "top_k": cfg.get("top_k", 50), "num_beams": cfg.get("num_beams", 1), "max_new_tokens": cfg.get("max_new_tokens", 1024),
            "repetition_penalty": cfg.get("repetition_penalty", 1.0), "length_penalty": cfg.get("length_penalty", 1.0)}
+    # HF's prompt-lookup decoding (llm_spec.py; opt-in, batch 1): the keys reach generate only when the YAML sets them
+    for key in ("prompt_lookup_num_tokens", "max_matching_ngram_size"):
+        if cfg.get(key) is not None:
+            gen[key] = cfg[key]
     generating_args = SimpleNamespace(**gen, to_dict=lambda: dict(gen))
     return model_args, data_args, training_args, finetuning_args, generating_args
 

@@ -147,6 +147,10 @@ class GraphedDecoder:
         self._cache_fused = False
         self._key = None
         self._graph = None
+        self._spec_graph = None         # prompt-lookup speculative step (_generate_spec): forward over k + 1 rows + verify + next draft
+        self._spec_key = None
+        self._spec_bufs = None
+        self.spec_stats = None          # {"forwards", "accepted", "tokens"} of the last speculative generate
         self._eager_keys = set()        # (batch, cache length) shapes whose step is not captured (_warm_up)
 
     def _host_read_rope(self):
@@ -169,7 +173,7 @@ class GraphedDecoder:
         warnings.warn(f"rope_type={rope_type} reads the position ids on the host and {why}: this decoder runs eagerly (no hipGraph) "
                       "from now on")
         self.use_graph = self.graph_suffix = False
-        self._graph = self._beam_graph = None
+        self._graph = self._beam_graph = self._spec_graph = None
         self._side_graphs = {}
 
     def _graph_on(self) -> bool:
@@ -192,8 +196,9 @@ class GraphedDecoder:
             self._graphs_off(rope_type, "the fused decode prologue is not installed" if "_ll_decode" not in base.__dict__
                              else "this decoder runs without the fused cache append that the fused prologue needs")
 
-    def _warm_up(self):
-        """The eager step on a side stream that precedes the capture of the decode step (its state is rewound).  For a rotary module that
+    def _warm_up(self, run=None):
+        """The eager step on a side stream that precedes the capture of the decode step (its state is rewound; ``run``: another step's
+        forward and rewind in place of the one-token step's).  For a rotary module that
         reads the device on the host this is also where the capture is decided: if the step was not served by the fused prologue (more
         rows than it takes, a layer that is not eligible at this shape, an embedding that is not bf16) HF's module ran, and the decoder
         runs this (batch, cache length) shape eagerly from then on (one warning per shape) instead of entering a capture with a host read
@@ -201,10 +206,13 @@ class GraphedDecoder:
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            self._step()
-            # the warm-up advanced the cache's on-device length counters; rewind them so that the captured step (replayed for this same
-            # token) writes the same slot again
-            self._rewind(self.tok.shape[1])
+            if run is not None:
+                run()
+            else:
+                self._step()
+                # the warm-up advanced the cache's on-device length counters; rewind them so that the captured step (replayed for this same
+                # token) writes the same slot again
+                self._rewind(self.tok.shape[1])
         torch.cuda.current_stream().wait_stream(s)
         rope_type = self._host_read_rope()
         if rope_type is not None and not self._served_by_fused_prologue():
@@ -212,7 +220,7 @@ class GraphedDecoder:
             warnings.warn(f"rope_type={rope_type} reads the position ids on the host and the fused decode prologue does not serve this "
                           f"model's step at {self.tok.shape[0]} rows: calls of this shape run eagerly (no hipGraph)")
             self._eager_keys.add(self._key)
-            self._graph = self._beam_graph = None
+            self._graph = self._beam_graph = self._spec_graph = None
 
     def _capture(self, attr: str, body) -> bool:
         """Capture ``body`` (the decode step and what follows it on the device) into a new graph stored as ``self.<attr>``.  A step that the
@@ -234,7 +242,7 @@ class GraphedDecoder:
             warnings.warn(f"hipGraph capture of the decode step failed ({type(e).__name__}: {why}); calls of this shape "
                           f"({self.tok.shape[0]} rows) run eagerly (no hipGraph)")
             self._eager_keys.add(self._key)
-            self._graph = self._beam_graph = None
+            self._graph = self._beam_graph = self._spec_graph = None
             torch.cuda.synchronize()
             return False
         setattr(self, attr, g)
@@ -270,6 +278,9 @@ class GraphedDecoder:
         self._beam_key = None           # beam search: state buffer (llm_beam.py) and the captured forward + beam step
         self._beam_graph = None
         self._graph = None
+        self._spec_graph = None         # prompt lookup: the captured speculative step and its static buffers (_generate_spec)
+        self._spec_key = None
+        self._spec_bufs = None
         # an MX8 cache on the device follows the fused convention from its construction (every layer at layer 0's counter, advanced per forward)
         self._cache_fused = self.kv_cache is not None and self.cache.shared_counter
         self._side_graphs = {}          # captured against the buffers above
@@ -452,17 +463,199 @@ class GraphedDecoder:
         self._last["n_new"] = n
         return self.out_buf[:, :n].clone()
 
+    # ------------------------------------------------------------------ prompt-lookup speculative decoding (llm_spec.py), one sequence
+    def _spec_forward(self, ids, cache_pos, pos_ids):
+        """Logits [S,V] of the S = k + 1 rows ``ids`` [1,S] at cache slots ``cache_pos``.  On a fused cache the query-token forward of the
+        fused layers serves it (llm_accel._suffix_forward: five launches per layer, the slot read from layer 0's counter on the device);
+        anywhere else -- a CPU model, layers=False, a declined layout -- HF's own forward runs the same rows."""
+        from .llm_accel import suffix_on_fused_layers
+        fused = self._cache_fused and suffix_on_fused_layers(self.model, True)
+        try:
+            out = self.model(input_ids=ids, attention_mask=self.mask, past_key_values=self.cache, cache_position=cache_pos,
+                             position_ids=pos_ids, use_cache=True, return_dict=True)
+        finally:
+            if fused:
+                suffix_on_fused_layers(self.model, False)
+        return out.logits[0]
+
+    def _spec_counters(self, pos):
+        """Every cache layer's next-slot counter to ``pos`` (int, or the device counter).  Only an unfused cache needs it after a step: its
+        layers each advanced by S, not by the accepted tokens (a fused cache has the one counter, which the verify launch sets)."""
+        for layer in self.cache.layers:
+            c = getattr(layer, "cumulative_length", None)
+            if c is not None:
+                c.fill_(pos) if isinstance(pos, int) else c.copy_(pos.reshape(c.shape))
+
+    def _generate_spec_torch(self, logits, spec, do_sample, temperature, top_p, top_k, eos_list, P, plen, max_new_tokens, generator, device,
+                             input_ids):
+        """The step of llm_spec.py op by op, host-driven (CPU models, sampler="torch", logits the HIP sampler does not take).  Row i is only
+        sampled while every earlier draft was accepted, so a generator advances once per emitted token, as in the plain torch loop."""
+        from .llm_spec import accept, draft_rows
+        k, n = spec
+        S = k + 1
+        eos_set = set(eos_list)
+
+        def pick(row):
+            return int(sample_top_p(row, temperature, top_p, generator, top_k)) if do_sample else int(row.argmax(dim=-1))
+        if self._sample_key is not None:     # as in the torch-sampler loop of generate
+            self._sample_key = None
+            self._graph = None
+        history = input_ids[0].tolist() if input_ids is not None else []
+        out = [pick(logits[:1])]
+        history.append(out[0])
+        done = out[0] in eos_set
+        pos, posid, forwards, accepted = P, int(plen[0, 0]), 0, 0
+        ar = torch.arange(S, device=device)
+        while not done and len(out) < max_new_tokens:
+            rows = draft_rows(history, out[-1], k, n)
+            self._spec_counters(pos)
+            logits = self._spec_forward(torch.tensor([rows], dtype=torch.long, device=device), pos + ar, (posid + ar).unsqueeze(0))
+            x = []
+            for i in range(S):
+                x.append(pick(logits[i:i + 1]))
+                if i >= k or x[i] != rows[i + 1] or x[i] in eos_set:
+                    break
+            emitted, done = accept(rows, x, eos_set, max_new_tokens - len(out))
+            out += emitted
+            history += emitted
+            pos += len(emitted)
+            posid += len(emitted)
+            forwards += 1
+            accepted += len(emitted) - 1
+        self._spec_counters(pos)
+        self.last_logits = logits
+        self._last["n_new"] = len(out)
+        self.spec_stats = {"forwards": forwards, "accepted": accepted, "tokens": len(out)}
+        return torch.tensor([out], dtype=torch.long, device=device)
+
+    def _generate_spec(self, logits, spec, sp, P, plen, eos_list, max_new_tokens, generator, device, input_ids):
+        """Decode loop of prompt-lookup decoding with the HIP step: per forward the host replays ONE graph = the model on the k + 1 static
+        rows, ll_spec_verify_bf16 (sample every row, accept, emit, bookkeeping) and, as that entry's tail, the next step's draft.  The
+        first token comes from the prefill logits through the plain sampler, the first draft from ll_spec_draft.  ``last_logits`` are the
+        [S,V] logits of the last forward."""
+        from . import _lib
+        from ._trace import mark
+        lib = _lib.load()
+        k, n = spec
+        S = k + 1
+        V = logits.shape[1]
+        cap = self.out_buf.shape[1]
+        stream = lambda: torch.cuda.current_stream().cuda_stream      # noqa: E731
+        if self._spec_bufs is None or self._spec_bufs["ids"].shape[1] != S:
+            z = lambda *shape: torch.zeros(*shape, dtype=torch.long, device=device)      # noqa: E731
+            # static buffers of the captured step: its input rows, the lookup history and its length, the sampled rows, counters
+            self._spec_bufs = dict(ids=z(1, S), posids=z(1, S), cpos=z(S), hist=z(cap), hist_len=z(1), xs=z(16), stats=z(2), max_new=z(1))
+            self._spec_graph = None
+        b = self._spec_bufs
+        self.done.zero_()
+        self.stepc.zero_()
+        self.out_buf.fill_(sp[3])
+        self.eos_buf.fill_(-1)
+        if eos_list:
+            self.eos_buf[:len(eos_list)] = torch.tensor(eos_list, dtype=torch.long, device=device)
+        gen_dev = generator.device.type if generator is not None else device.type
+        self.seed_buf.copy_(torch.randint(0, 2 ** 62, (1,), device=gen_dev, generator=generator))
+        self.posid.copy_(plen)
+        self.pos.fill_(P)
+        b["stats"].zero_()
+        b["max_new"].fill_(max_new_tokens)
+        if input_ids is not None:                   # the history starts from the call's input_ids row as given, or empty (inputs_embeds)
+            b["hist"][:P] = input_ids[0]
+        b["hist_len"].fill_(P if input_ids is not None else 0)
+        self._hip_sample(logits, sp, 0)             # first token, from the prefill logits: step = 1
+        rc = lib.ll_spec_draft(b["hist"].data_ptr(), cap, b["hist_len"].data_ptr(), self.tok.data_ptr(), 1, k, n, self.pos.data_ptr(),
+                               self.posid.data_ptr(), b["ids"].data_ptr(), b["posids"].data_ptr(), b["cpos"].data_ptr(), stream())
+        if rc != 0:
+            _lib.check(rc, "ll_spec_draft")
+        mark("generate: first token sampled")
+        greedy, inv_temp, top_p, _, top_k, _ = sp
+
+        def forward():
+            return self._spec_forward(b["ids"], b["cpos"], b["posids"])
+
+        def verify(lg):
+            fused = self._cache_fused
+            rc = lib.ll_spec_verify_bf16(lg.data_ptr(), lg.stride(0), S, V, inv_temp, top_p, int(top_k), int(greedy), self.seed_buf.data_ptr(),
+                                         self.eos_buf.data_ptr(), N_EOS_SLOTS, self.done.data_ptr(), self.tok.data_ptr(),
+                                         self.out_buf.data_ptr(), cap, b["max_new"].data_ptr(), self.stepc.data_ptr(), self.posid.data_ptr(),
+                                         self.pos.data_ptr(), self.cache.layers[0].cumulative_length.data_ptr() if fused else None,
+                                         b["ids"].data_ptr(), b["posids"].data_ptr(), b["cpos"].data_ptr(), b["hist"].data_ptr(), cap,
+                                         b["hist_len"].data_ptr(), n, 1, b["stats"].data_ptr(), b["xs"].data_ptr(), stream())
+            if rc != 0:
+                _lib.check(rc, "ll_spec_verify_bf16")
+            if not fused:
+                self._spec_counters(self.pos)
+
+        def warm():             # the forward only; an unfused cache's layers advanced by S (a fused cache's counter is not touched)
+            forward()
+            if not self._cache_fused:
+                for layer in self.cache.layers:
+                    layer.cumulative_length.sub_(S)
+
+        def body():
+            self.logits = forward()
+            verify(self.logits)
+
+        gkey = (k, n, sp, self._cache_fused)        # the captured launches hold these by value
+        if self._spec_key != gkey:
+            self._spec_key = gkey
+            self._spec_graph = None
+        left, until = max_new_tokens - 1, 0         # tokens still to emit as of the last host read; replays until the next one
+        while left > 0:
+            if until == 0:
+                # at most every sync_every replays, and no later than the fewest replays that can finish the call (S tokens each):
+                # a replay after the end changes nothing but costs a forward
+                until = max(1, min(self.sync_every, -(-left // S)))
+            if self._graph_on() and self._spec_graph is None:
+                self._warm_up(warm)
+            if self._graph_on() and self._spec_graph is None:
+                self._capture("_spec_graph", body)
+            if self._graph_on():
+                self._spec_graph.replay()
+                logits = self.logits
+            else:
+                logits = forward()
+                verify(logits)
+            until -= 1
+            if until == 0:
+                done, step = torch.stack([self.done[0].long(), self.stepc[0]]).tolist()       # one host read
+                left = 0 if done else max_new_tokens - step
+                mark("generate: rendezvous")
+        step, forwards, accepted = torch.cat([self.stepc, b["stats"]]).tolist()
+        self.last_logits = logits
+        self._last["n_new"] = step
+        self.spec_stats = {"forwards": forwards, "accepted": accepted, "tokens": step}
+        return self.out_buf[:, :step].clone()
+
     @torch.no_grad()
     def generate(self, input_ids: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
                  inputs_embeds: Optional[torch.Tensor] = None, max_new_tokens: int = 128, do_sample: bool = True,
                  temperature: float = 1.0, top_p: float = 1.0, eos_token_id: Optional[Sequence[int]] = None,
                  pad_token_id: Optional[int] = None, generator=None, top_k: Optional[int] = None,
                  repetition_penalty: Optional[float] = None, num_beams: Optional[int] = None, length_penalty: Optional[float] = None,
-                 early_stopping=None, **other) -> torch.Tensor:
+                 early_stopping=None, prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
+                 **other) -> torch.Tensor:
         # HF RepetitionPenaltyLogitsProcessor: every token of the call's input_ids (prompt, pads included, then each generated token;
         # an inputs_embeds call starts from none) gets x < 0 ? x * p : x / p ahead of the sampling options below
         penalty = check_repetition_penalty(repetition_penalty)
         penalty = 1.0 if penalty is None else penalty
+        # HF's prompt-lookup decoding (llm_spec.py): opt-in, one sequence; absent / None / 0 = the plain decode, not one launch changed
+        from .llm_spec import check_prompt_lookup
+        spec = check_prompt_lookup(prompt_lookup_num_tokens, max_matching_ngram_size)
+        beams = num_beams is not None and (isinstance(num_beams, bool) or num_beams != 1)
+        rows = (input_ids if input_ids is not None else inputs_embeds).shape[0]
+        if spec is None and os.environ.get("LLAMOLE_PROMPT_LOOKUP") and rows == 1 and not beams and penalty == 1.0:
+            # A/B switch (like LLAMOLE_KV_CACHE): every call that can take prompt lookup runs with k = its value, the default ngram size
+            spec = check_prompt_lookup(int(os.environ["LLAMOLE_PROMPT_LOOKUP"]), None)
+        if spec is not None:
+            if rows != 1:
+                raise ValueError(f"GraphedDecoder.generate: prompt_lookup_num_tokens needs a batch of 1 sequence, got {rows} (HF's assisted "
+                                 "generation is batch-1 only as well)")
+            if beams:
+                raise NotImplementedError("GraphedDecoder.generate does not implement prompt_lookup_num_tokens together with num_beams > 1")
+            if penalty != 1.0:
+                raise NotImplementedError("GraphedDecoder.generate does not implement prompt_lookup_num_tokens together with "
+                                          "repetition_penalty != 1 (the seen set of a row would depend on the accepted prefix)")
         if num_beams is not None and (isinstance(num_beams, bool) or num_beams != 1):
             nb, es = check_beam_options(num_beams, early_stopping)
             if self.kv_cache is not None:
@@ -492,7 +685,8 @@ class GraphedDecoder:
             attention_mask = torch.ones(B, P, dtype=torch.long, device=device)
         # static-cache length rounded up to a bucket: prompts of slightly different lengths (A* expansion prompts, eval
         # batches) then share one cache allocation and ONE captured graph; unused tail slots stay masked by causality
-        max_len = -(-(P + max_new_tokens) // self.len_bucket) * self.len_bucket
+        # (prompt lookup: k slots of slack -- the last step's rejected drafts write K/V past the last emitted token)
+        max_len = -(-(P + max_new_tokens + (spec[0] if spec is not None else 0)) // self.len_bucket) * self.len_bucket
         self._prepare(B, max_len, device, inputs_embeds is not None)
         self._last = None
         eos = torch.tensor(list(eos_token_id) if isinstance(eos_token_id, (list, tuple)) else
@@ -522,13 +716,22 @@ class GraphedDecoder:
         if self.fused_cache and not self._cache_fused and device.type == "cuda":
             from .llm_accel import fuse_cache_update
             self._cache_fused = fuse_cache_update(self.cache) > 0
-        if (self.sampler == "hip" and logits.is_cuda and logits.dtype == torch.bfloat16 and logits.shape[1] % 8 == 0
-                and logits.shape[1] <= MAX_HIP_VOCAB and logits.stride(1) == 1 and eos.numel() <= N_EOS_SLOTS
-                and (not do_sample or (temperature or 1.0) > 0)):
+        hip_sampler = (self.sampler == "hip" and logits.is_cuda and logits.dtype == torch.bfloat16 and logits.shape[1] % 8 == 0
+                       and logits.shape[1] <= MAX_HIP_VOCAB and logits.stride(1) == 1 and eos.numel() <= N_EOS_SLOTS
+                       and (not do_sample or (temperature or 1.0) > 0))
+        if spec is not None and not hip_sampler:
+            new_tokens = self._generate_spec_torch(logits, spec, do_sample, temperature, top_p, top_k, eos.tolist(), P, plen, max_new_tokens,
+                                                   generator, device, input_ids)
+            return torch.cat([input_ids, new_tokens], dim=1) if input_ids is not None else new_tokens
+        if hip_sampler:
             import numpy as np
             temp = 1.0 if temperature is None else float(temperature)
             sp = (not do_sample, float(np.float32(1.0) / np.float32(temp)), 1.0 if top_p is None else float(top_p), int(pad), top_k,
                   float(np.float32(penalty)))
+            if spec is not None:
+                new_tokens = self._generate_spec(logits, spec, sp, P, plen, eos.tolist(), max_new_tokens, generator, device, input_ids)
+                mark("generate: decode loop done")
+                return torch.cat([input_ids, new_tokens], dim=1) if input_ids is not None else new_tokens
             new_tokens = self._generate_hip(logits, sp, P, plen, eos.tolist(), max_new_tokens, generator, device, input_ids)
             mark("generate: decode loop done")
             return torch.cat([input_ids, new_tokens], dim=1) if input_ids is not None else new_tokens

@@ -95,6 +95,8 @@ class GraphLLMForCausalMLM(nn.Module):
         return info
 
     def _llm_generate(self, inputs=None, attention_mask=None, inputs_embeds=None, **kwargs):
+        """Every generation option (``prompt_lookup_num_tokens`` / ``max_matching_ngram_size`` of HF's prompt-lookup decoding included) goes
+        to the graphed decoder, or on the HF path to ``language_model.generate``, unchanged."""
         if self.decoder is not None:
             return self.decoder.generate(input_ids=inputs, attention_mask=attention_mask, inputs_embeds=inputs_embeds, **kwargs)
         if inputs_embeds is not None:
