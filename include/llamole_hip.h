@@ -327,6 +327,38 @@ int ll_suffix_attn_rope_split_bf16(const void *qkv, int64_t ld_qkv, const void *
                                    const void *mask, void *out, int B, int S, int nh, int nkv, int maxlen, int D, float scale,
                                    const void *q_norm_w, const void *k_norm_w, float eps, void *workspace, int64_t workspace_bytes,
                                    void *stream);
+/* ---- the key-split calls for sliding-window layers (Mistral-v0.1, Qwen2 / Qwen3 with use_sliding_window) ------------------------------------
+ * ll_decode_attn_rope_win_bf16 : the arguments of ll_decode_attn_rope_split_bf16 with `int window` in front of the workspace.
+ * ll_suffix_attn_rope_win_bf16 : likewise for ll_suffix_attn_rope_split_bf16.
+ *     Semantics: HF's sliding_window_causal_mask_function over cache slots.  Key j is visible to query row r = b*S + s iff mask[r][j] != 0 and
+ *     j > *pos + s - window; the mask is the one the prologues write (causal and padding) and the window is applied in the kernel, so one
+ *     prologue launch serves the full and the sliding layers of a mixed model.  Everything else is the contract of the split entries: *pos is
+ *     read on the device; the new rows are rotated in the launch and no workgroup reads slots *pos .. *pos+S-1 from the cache; each new row is
+ *     stored by exactly one workgroup, bit for bit the row the entry points above store (a row is stored whether or not a window sees it); no
+ *     atomics, fixed summation orders; a row without a visible key gives exact zeros; masked slots and slots below the window may hold
+ *     anything (NaN); q_norm_w / k_norm_w as above.
+ *     Geometry, a function of (B, S, nh, nkv, maxlen, D, window) only, so a captured graph replays it at every position:
+ *       1. partial: nrw = min(ceil(maxlen/512), ceil((window + S - 2)/512) + 1) ranges per (head group, row) instead of ceil(maxlen/512).
+ *          Workgroup x takes the ABSOLUTE range first + x, first = max(0, *pos - window + 1) / 512 computed on the device: ranges stay aligned to
+ *          multiples of 512 slots.  The S windows of a call span at most window + S - 1 consecutive slots, which touch at most nrw such ranges.
+ *          A range index past the end of the cache writes the empty partial (-inf, 0); mask bytes below the window are not read.
+ *       2. combine: over the nrw ranges, with the operands and the order the split combine has over all ranges of the cache.
+ *     Hence the output is bit for bit that of the split entry called with the window cut out of its mask, and with window >= *pos + S that of
+ *     the split entry on the same mask.
+ *     Bounds: 1 <= window (any int: a window the cache cannot fill costs the split entries' geometry); D, nh, nkv, B, S, maxlen, ld_qkv and the
+ *     alignment as for the split entries; workspace_bytes >= ll_attn_win_workspace_bytes.  Beyond them LL_EINVAL (ll_attn_win_workspace_bytes:
+ *     -1) and nothing is launched.
+ * ll_attn_win_workspace_bytes : bytes of the workspace for these sizes (decode: S = 1): B*S*nh*nrw*(D+2) f32; its layout is private.  Calls on
+ *     one stream may share one workspace. */
+int64_t ll_attn_win_workspace_bytes(int B, int S, int nh, int nkv, int maxlen, int D, int window);
+int ll_decode_attn_rope_win_bf16(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, int64_t cs_stride, void *Kc, void *Vc,
+                                 const int64_t *pos, const void *mask, int64_t mask_stride, void *out, int B, int nh, int nkv, int maxlen,
+                                 int D, float scale, const void *q_norm_w, const void *k_norm_w, float eps, int window, void *workspace,
+                                 int64_t workspace_bytes, void *stream);
+int ll_suffix_attn_rope_win_bf16(const void *qkv, int64_t ld_qkv, const void *cos, const void *sin, void *Kc, void *Vc, const int64_t *pos,
+                                 const void *mask, void *out, int B, int S, int nh, int nkv, int maxlen, int D, float scale,
+                                 const void *q_norm_w, const void *k_norm_w, float eps, int window, void *workspace, int64_t workspace_bytes,
+                                 void *stream);
 /* ---- the microscaled FP8 (OCP MXFP8) KV cache: a static cache of D + D/32 bytes per row instead of 2 D ------------------------------------
  * Storage, per cache layer four contiguous uint8 tensors: K codes and V codes [B,nkv,maxlen,D] (FP8 E4M3, OCP e4m3fn) and K scales and
  *     V scales [B,nkv,maxlen,D/32] (E8M0: the byte e + 127 of the scale 2^e shared by 32 consecutive elements of head_dim).  The stored row of a

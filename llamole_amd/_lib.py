@@ -88,6 +88,9 @@ SIGNATURES = {
     "ll_attn_split_workspace_bytes": (_I64, [_I, _I, _I, _I, _I, _I]),
     "ll_decode_attn_rope_split_bf16": (_I, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _I64, _P, _I, _I, _I, _I, _I, _F, _P, _P, _F, _P, _I64, _P]),
     "ll_suffix_attn_rope_split_bf16": (_I, [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _F, _P, _I64, _P]),
+    "ll_attn_win_workspace_bytes": (_I64, [_I, _I, _I, _I, _I, _I, _I]),
+    "ll_decode_attn_rope_win_bf16": (_I, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _I64, _P, _I, _I, _I, _I, _I, _F, _P, _P, _F, _I, _P, _I64, _P]),
+    "ll_suffix_attn_rope_win_bf16": (_I, [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _F, _I, _P, _I64, _P]),
     "ll_kv8_store_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(_I64), C.POINTER(_I64), _P]),
     "ll_kv8_load_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ll_decode_attn_rope_kv8": (_I, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _P, _I, _I, _I, _I, _I, _F, _P, _P, _F, _P, _I64, _P]),

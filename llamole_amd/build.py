@@ -18,7 +18,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libllamole_hip.so")
 TUNING_LIB = os.path.join(HERE, "libllamole_hip_tuning.so")
 SOURCES = ["gemm.hip", "graphdit.hip", "gin.hip", "llm_ops.hip", "llm_layer.hip", "llm_attn.hip", "llm_rows16.hip", "llm_rows64.hip", "llm_sample.hip",
-           "llm_beam.hip", "llm_wq.hip", "llm_moe.hip", "llm_attn_split.hip", "llm_attn_kv8.hip", "llm_spec.hip"]
+           "llm_beam.hip", "llm_wq.hip", "llm_moe.hip", "llm_attn_split.hip", "llm_attn_kv8.hip", "llm_spec.hip",
+           "llm_attn_win.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
          "-mllvm", "-amdgpu-kernarg-preload-count=16"]
 JOBS = max(1, min(8, (os.cpu_count() or 2)))

@@ -63,6 +63,18 @@ LLM_CONFIGS = {
                          intermediate_size=512, vocab_size=2048, max_position_embeddings=2048, rope_theta=10000.0,
                          rms_norm_eps=1e-5, tie_word_embeddings=False, embedding_multiplier=12.0, attention_multiplier=0.0078125,
                          residual_multiplier=0.22, logits_scaling=8.0),
+    # sliding-window attention.  "mistral-7b-v0.1": every layer sees the last 4096 positions; widths, vocabulary and window are written from
+    # memory of the published mistralai/Mistral-7B-v0.1 config.json, not read from it.  "tiny-qwen2-sw": the Qwen2 / Qwen3 mix through
+    # use_sliding_window / max_window_layers -- layer 0 full, layer 1 sliding (config.layer_types)
+    "mistral-7b-v0.1": dict(cls="Mistral", hidden_size=4096, num_hidden_layers=32, num_attention_heads=32, num_key_value_heads=8,
+                            intermediate_size=14336, vocab_size=32000, max_position_embeddings=32768, rope_theta=10000.0,
+                            rms_norm_eps=1e-5, sliding_window=4096, tie_word_embeddings=False),
+    "tiny-mistral-sw": dict(cls="Mistral", hidden_size=256, num_hidden_layers=2, num_attention_heads=2, num_key_value_heads=1,
+                            intermediate_size=512, vocab_size=2048, max_position_embeddings=2048, rope_theta=10000.0,
+                            rms_norm_eps=1e-5, sliding_window=24, tie_word_embeddings=False),
+    "tiny-qwen2-sw": dict(cls="Qwen2", hidden_size=256, num_hidden_layers=2, num_attention_heads=4, num_key_value_heads=2,
+                          intermediate_size=512, vocab_size=2048, max_position_embeddings=2048, rope_theta=10000.0,
+                          rms_norm_eps=1e-6, tie_word_embeddings=False, use_sliding_window=True, sliding_window=24, max_window_layers=1),
 }
 
 # rope_parameters of the published meta-llama/Meta-Llama-3.1-8B-Instruct config.json (rope_scaling there): the "llama-3.1-8b" entry above has the

@@ -42,6 +42,32 @@ def check_kv_cache(v) -> Optional[str]:
     return v
 
 
+def cache_layer_types(config) -> list:
+    """The kind of every cache layer of ``config`` as transformers' ``StaticCache`` would dispatch it ("full_attention", "sliding_attention",
+    ...): ``layer_types`` where the config has them, else derived from ``sliding_window`` (Mistral-v0.1: every layer sliding)."""
+    from transformers.cache_utils import get_layer_types_and_kwargs
+    return list(get_layer_types_and_kwargs(config.get_text_config(decoder=True))[0])
+
+
+class FullLengthStaticCache(StaticCache):
+    """A static cache in which EVERY layer is a full-length ``StaticLayer`` of ``max_cache_len`` slots, for a config with sliding-window layers.
+    transformers' own choice for those, ``StaticSlidingWindowLayer``, keeps its length in a Python int and picks its branch on the host (index
+    copy while filling, ``roll`` once full): a captured graph would replay whichever branch ran at capture time.  Here slot j always holds
+    position j; the window is applied by the mask (HF's sliding mask over ``get_mask_sizes() == (max_cache_len, 0)``) or inside the windowed
+    attention kernels.  All slots are kept: no memory is saved (a ring buffer is not what this is)."""
+
+    def __init__(self, config, max_cache_len: int):
+        Cache.__init__(self, layers=[StaticLayer(max_cache_len=max_cache_len) for _ in cache_layer_types(config)])
+
+
+def static_cache_for(config, max_cache_len: int) -> StaticCache:
+    """The bf16 static cache of the graphed decode: transformers' ``StaticCache`` for a config whose layers are all full attention, a
+    ``FullLengthStaticCache`` for one with sliding-window layers."""
+    if any(k != "full_attention" for k in cache_layer_types(config)):
+        return FullLengthStaticCache(config, max_cache_len)
+    return StaticCache(config=config, max_cache_len=max_cache_len)
+
+
 def mx8_cache_bytes(B: int, nkv: int, maxlen: int, D: int, layers: int) -> int:
     """Bytes of the codes and scales of an MX8 cache (the shared staging pair, one bf16 layer, comes on top)."""
     return 2 * layers * B * nkv * maxlen * (D + D // BLOCK)
@@ -134,9 +160,11 @@ class MX8StaticCache(StaticCache):
 
     def __init__(self, config, batch_size: int, max_cache_len: int, device, dtype=torch.bfloat16):
         cfg = config.get_text_config(decoder=True)
-        kinds = getattr(cfg, "layer_types", None)
-        if kinds is not None and any(k != "full_attention" for k in kinds):
-            raise ValueError("MX8StaticCache serves full-attention layers only")
+        kinds = cache_layer_types(cfg)
+        if any(k != "full_attention" for k in kinds):
+            raise ValueError(f"MX8StaticCache serves full-attention layers only: kv_cache=\"mxfp8\" cannot be combined with a model whose "
+                             f"config has layers of other kinds (sliding_window={getattr(cfg, 'sliding_window', None)!r}, layer types "
+                             f"{sorted(set(kinds))}); use kv_cache=None for it")
         nkv = getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
         D = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
         if D not in HEAD_DIMS:

@@ -689,6 +689,9 @@ class _FusedLayer:
         self.nh, self.nkv = self.nq // self.D, self.nkv_dim // self.D
         self.H = q.in_features
         self.scaling = float(att.scaling)
+        # a sliding-window layer (Mistral-v0.1, Qwen2 / Qwen3 layer_types): key j is seen from slot p iff j > p - window, applied inside the
+        # windowed key-split entries (ll_*_attn_rope_win_bf16) wherever the window can bind (``_windowed``); None = full attention
+        self.window = attn_window(att)
         # Granite layout: both residual adds are residual + y * residual_multiplier; None = the plain residual epilogue (absent or 1.0)
         rm = _multiplier(layer, "residual_multiplier")[0]
         self.rscale = None if rm == 1.0 else rm
@@ -815,25 +818,36 @@ class _FusedLayer:
             _lib.check(rc, "ll_gemv_fused_bf16")
         return out
 
+    def _windowed(self, maxlen: int) -> bool:
+        """Whether the window can bind on a static cache of ``maxlen`` slots: then the windowed entries run, at every cache length.  With
+        ``window >= maxlen`` every slot a causal mask shows lies inside the window and the layer takes exactly a full-attention layer's calls."""
+        return self.window is not None and self.window < maxlen
+
     def attn_serves(self, B: int, S: int, maxlen: int, kv8: bool = False) -> bool:
         """Whether this layer's attention entry points take a static cache of ``maxlen`` slots for B sequences of S new positions: up to
         ATTN_MAXLEN the one-workgroup kernels, beyond it whatever the key-split entry accepts (its own answer, asked once per shape).  An MX8
-        cache (``kv8``) has the key-split entries only, at every length, with the same bounds."""
-        if maxlen <= ATTN_MAXLEN and not kv8:
+        cache (``kv8``) has the key-split entries only, at every length, with the same bounds; so has a sliding-window layer whose window can
+        bind (the windowed entries; there are none for an MX8 cache)."""
+        win = self._windowed(maxlen)
+        if win and kv8:         # (kv_cache.MX8StaticCache refuses a config with sliding layers, so no such cache comes from GraphedDecoder)
+            return False
+        if maxlen <= ATTN_MAXLEN and not kv8 and not win:
             return True
         key = (B, S, maxlen)
         if key not in self._split_ok:
-            self._split_ok[key] = int(self.lib.ll_attn_split_workspace_bytes(B, S, self.nh, self.nkv, maxlen, self.D)) >= 0 and \
-                (S > 1 or B <= MAX_STREAM_ROWS)
+            n = (self.lib.ll_attn_win_workspace_bytes(B, S, self.nh, self.nkv, maxlen, self.D, self.window) if win else
+                 self.lib.ll_attn_split_workspace_bytes(B, S, self.nh, self.nkv, maxlen, self.D))
+            self._split_ok[key] = int(n) >= 0 and (S > 1 or B <= MAX_STREAM_ROWS)
         return self._split_ok[key]
 
     def _split_workspace(self, B: int, S: int, maxlen: int, device):
         """The model's workspace of the key-split attention for this shape: allocated at the first call (the eager step that precedes a capture),
         shared by the layers, which run one after the other on one stream; a captured graph holds its fixed address."""
-        key = (B, S, self.nh, self.nkv, maxlen, self.D, str(device))
+        window = self.window if self._windowed(maxlen) else None
+        key = (B, S, self.nh, self.nkv, maxlen, self.D, str(device), window)
         ws = self._split_ws.get(key)
         if ws is None:
-            ws = self._split_ws[key] = _AttnSplitWorkspace(self.lib, device, B, S, self.nh, self.nkv, maxlen, self.D)
+            ws = self._split_ws[key] = _AttnSplitWorkspace(self.lib, device, B, S, self.nh, self.nkv, maxlen, self.D, window)
         return ws
 
     def _split_tail(self, B: int, S: int, maxlen: int, device):
@@ -841,7 +855,8 @@ class _FusedLayer:
         ws = self._split_workspace(B, S, maxlen, device)
         qn = self.qn.weight.data_ptr() if self.qn is not None else None
         kn = self.kn.weight.data_ptr() if self.kn is not None else None
-        return (qn, kn, self.qk_eps, ws.t.data_ptr(), ws.bytes, torch.cuda.current_stream().cuda_stream)
+        win = (self.window,) if self._windowed(maxlen) else ()      # the windowed entries take the window in front of the workspace
+        return (qn, kn, self.qk_eps, *win, ws.t.data_ptr(), ws.bytes, torch.cuda.current_stream().cuda_stream)
 
     def _attn(self, qkv, nqkv, mask, cache, pe, B, device):
         cl = cache.layers[self.layer_idx]
@@ -855,6 +870,9 @@ class _FusedLayer:
             name = "ll_decode_attn_rope_kv8"
             rc = self.lib.ll_decode_attn_rope_kv8(*args[:5], cl.keys.data_ptr(), cl.key_scales.data_ptr(), cl.values.data_ptr(),
                                                   cl.value_scales.data_ptr(), *args[7:], *self._split_tail(B, 1, cl.keys.shape[2], device))
+        elif self._windowed(cl.keys.shape[2]):    # a window that can bind: only the ranges of 512 keys it can reach, at every cache length
+            name = "ll_decode_attn_rope_win_bf16"
+            rc = self.lib.ll_decode_attn_rope_win_bf16(*args, *self._split_tail(B, 1, cl.keys.shape[2], device))
         elif cl.keys.shape[2] > ATTN_MAXLEN:      # beyond the one-workgroup kernels: the keys split over workgroups, two launches
             name = "ll_decode_attn_rope_split_bf16"
             rc = self.lib.ll_decode_attn_rope_split_bf16(*args, *self._split_tail(B, 1, cl.keys.shape[2], device))
@@ -926,6 +944,9 @@ class _FusedLayer:
             name = "ll_suffix_attn_rope_kv8"
             rc = self.lib.ll_suffix_attn_rope_kv8(*args[:4], cl.keys.data_ptr(), cl.key_scales.data_ptr(), cl.values.data_ptr(),
                                                   cl.value_scales.data_ptr(), *args[6:], *self._split_tail(B, S, cl.keys.shape[2], h.device))
+        elif self._windowed(cl.keys.shape[2]):
+            name = "ll_suffix_attn_rope_win_bf16"
+            rc = self.lib.ll_suffix_attn_rope_win_bf16(*args, *self._split_tail(B, S, cl.keys.shape[2], h.device))
         elif cl.keys.shape[2] > ATTN_MAXLEN:
             name = "ll_suffix_attn_rope_split_bf16"
             rc = self.lib.ll_suffix_attn_rope_split_bf16(*args, *self._split_tail(B, S, cl.keys.shape[2], h.device))
@@ -944,12 +965,16 @@ class _FusedLayer:
 
 class _AttnSplitWorkspace:
     """Device scratch of ``ll_decode_attn_rope_split_bf16`` / ``ll_suffix_attn_rope_split_bf16`` (per-range softmax statistics and partial
-    outputs) for one shape; one per model and shape, allocated once, so a captured graph holds a fixed address."""
+    outputs) for one shape, or with a ``window`` that of the windowed entries (sized by the ranges a window reaches); one per model and shape,
+    allocated once, so a captured graph holds a fixed address."""
 
-    def __init__(self, lib, device, B, S, nh, nkv, maxlen, D):
-        n = int(lib.ll_attn_split_workspace_bytes(B, S, nh, nkv, maxlen, D))
+    def __init__(self, lib, device, B, S, nh, nkv, maxlen, D, window=None):
+        if window is None:
+            name, n = "ll_attn_split_workspace_bytes", int(lib.ll_attn_split_workspace_bytes(B, S, nh, nkv, maxlen, D))
+        else:
+            name, n = "ll_attn_win_workspace_bytes", int(lib.ll_attn_win_workspace_bytes(B, S, nh, nkv, maxlen, D, window))
         if n < 0:
-            raise ValueError(f"ll_attn_split_workspace_bytes: unsupported sizes B={B} S={S} nh={nh} nkv={nkv} maxlen={maxlen} D={D}")
+            raise ValueError(f"{name}: unsupported sizes B={B} S={S} nh={nh} nkv={nkv} maxlen={maxlen} D={D} window={window}")
         self.bytes = n
         self.t = torch.empty(n, dtype=torch.uint8, device=device)
 
@@ -1118,6 +1143,28 @@ def _moe_block_declined(mlp, hidden: int) -> Optional[str]:
     return None
 
 
+def attn_window(att):
+    """The sliding window of an HF attention module, None for full attention: its ``sliding_window`` attribute where the class has one (Qwen2 /
+    Qwen3 / Ministral: None on the full layers of a mixed model), else its config's -- MistralAttention keeps none and hands
+    ``config.sliding_window`` to the attention call."""
+    if hasattr(att, "sliding_window"):
+        return att.sliding_window
+    return getattr(getattr(att, "config", None), "sliding_window", None)
+
+
+def _config_window(att):
+    """The window HF's mask construction applies to this attention module's layer, read off the module's config: ``sliding_window`` where
+    ``layer_types`` names the layer "sliding_attention" (Qwen2 / Qwen3 / Ministral), or for a config without ``layer_types`` on every layer
+    (Mistral); None = a full causal mask."""
+    cfg = getattr(att, "config", None)
+    types = getattr(cfg, "layer_types", None)
+    if types is not None:
+        idx = getattr(att, "layer_idx", None)
+        if not (isinstance(idx, int) and 0 <= idx < len(types) and types[idx] == "sliding_attention"):
+            return None
+    return getattr(cfg, "sliding_window", None)
+
+
 def decoder_layer_declined(layer: nn.Module) -> Optional[str]:
     """Why ``fuse_decoder_layers`` would not fuse this decoder layer (None: it would) -- the sibling of ``model_decode_declined``.  Structural
     reasons come first and dtype / device reasons last, so the layout of a model can be judged on the CPU."""
@@ -1145,7 +1192,12 @@ def decoder_layer_declined(layer: nn.Module) -> Optional[str]:
         return "hidden size is not a multiple of 8 up to 8192"
     if not moe and (mlp.gate_proj.bias is not None or mlp.up_proj.bias is not None or mlp.down_proj.bias is not None):
         return "MLP bias"
-    if getattr(att, "sliding_window", None) is not None:
+    win = attn_window(att)
+    if win is not None and not (type(win) is int and win >= 1):
+        return f"sliding_window={win!r} is not a positive int"
+    if win != _config_window(att):
+        # a window on the module that its config does not state for this layer: HF builds the masks of the prompt pass and of the op-by-op
+        # decode from the config, so the windowed kernels would decode another model than the prefill filled the cache for
         return "sliding-window layer"
     why = _head_norm_declined(att)
     if why is not None:
@@ -1219,7 +1271,7 @@ def _model_forward(self, input_ids=None, attention_mask=None, position_ids=None,
             and getattr(past_key_values, "layers", None) and all(getattr(l, "_ll_fused_update", False) for l in past_key_values.layers)
             and attention_mask.shape[1] == past_key_values.layers[0].keys.shape[2]
             and (past_key_values.layers[0].keys.dtype == torch.bfloat16 or _is_kv8(past_key_values.layers[0]))
-            and layers[0]._ll_fused.attn_serves(input_ids.shape[0], 1, attention_mask.shape[1], _is_kv8(past_key_values.layers[0]))):
+            and all(f.attn_serves(input_ids.shape[0], 1, attention_mask.shape[1], _is_kv8(past_key_values.layers[0])) for f in st["attn_kinds"])):
         B, maxlen, D = input_ids.shape[0], attention_mask.shape[1], st["D"]
         dev = input_ids.device
         h = _embed(self, st, input_ids)
@@ -1267,8 +1319,8 @@ def _model_forward(self, input_ids=None, attention_mask=None, position_ids=None,
     clayers = getattr(past_key_values, "layers", None)
     keys = getattr(clayers[0], "keys", None) if clayers else None
     if input_ids is not None and input_ids.dim() == 2 and input_ids.shape[1] <= MAX_APPEND_ROWS and keys is not None and keys.dim() == 4 \
-            and (keys.shape[2] > ATTN_MAXLEN or _is_kv8(clayers[0])) \
-            and not layers[0]._ll_fused.attn_serves(input_ids.shape[0], input_ids.shape[1], keys.shape[2], _is_kv8(clayers[0])):
+            and (keys.shape[2] > ATTN_MAXLEN or _is_kv8(clayers[0]) or any(f._windowed(keys.shape[2]) for f in st["attn_kinds"])) \
+            and not all(f.attn_serves(input_ids.shape[0], input_ids.shape[1], keys.shape[2], _is_kv8(clayers[0])) for f in st["attn_kinds"]):
         st["declined"] = (f"decoder_layers: a static cache of {keys.shape[2]} slots ({input_ids.shape[0]} x {input_ids.shape[1]} new positions) is "
                           f"outside the bounds of the key-split attention (at most {ATTN_SPLIT_MAXLEN} slots, {MAX_STREAM_ROWS} sequences at decode)")
     return self._ll_model_orig(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
@@ -1310,7 +1362,7 @@ def _suffix_forward(self, st, layers, input_ids, attention_mask, position_ids, c
             and position_ids is not None and position_ids.shape == input_ids.shape and position_ids.dtype == torch.long
             and not kwargs.get("output_hidden_states") and not kwargs.get("output_attentions")
             and all(l._ll_fused.stream_ok for l in layers)
-            and layers[0]._ll_fused.attn_serves(B, S, attention_mask.shape[1], _is_kv8(clayers[0]))):
+            and all(f.attn_serves(B, S, attention_mask.shape[1], _is_kv8(clayers[0])) for f in st["attn_kinds"])):
         return None
     h = _embed(self, st, input_ids)
     if h.dtype != torch.bfloat16 or not h.is_contiguous():
@@ -1383,8 +1435,6 @@ def model_decode_declined(model: nn.Module) -> Optional[str]:
         return f"rope_type={rope_type}"
     if not hasattr(rot, "inv_freq") or rot.inv_freq.dtype != torch.float32 or not rot.inv_freq.is_cuda:
         return "inv_freq is not an f32 device tensor"
-    if getattr(base, "has_sliding_layers", False):
-        return "sliding-window layers"
     if rot.inv_freq.numel() * 2 != layers[0]._ll_fused.D:
         return "partial rotary dimension"
     if rope_type == "dynamic":
@@ -1416,6 +1466,12 @@ def fuse_model_decode(model: nn.Module) -> bool:
     # the output class of the base model's own forward: a MoE model's causal-LM head reads `router_logits` (None here) off it
     out_cls = getattr(sys.modules.get(type(base).__module__), "MoeModelOutputWithPast", BaseModelOutputWithPast)
     base._ll_decode = {"lib": _lib.load(), "D": base.layers[0]._ll_fused.D, "out_cls": out_cls}
+    # one fused layer per attention kind (full, or a sliding window): the layers of a model share every other size, so these answer for all of
+    # them whether the attention entries take a shape (``attn_serves``)
+    kinds = {}
+    for l in base.layers[: base.config.num_hidden_layers]:
+        kinds.setdefault(l._ll_fused.window, l._ll_fused)
+    base._ll_decode["attn_kinds"] = tuple(kinds.values())
     em = _multiplier(base, "embedding_multiplier")[0]
     if em != 1.0:
         base._ll_decode["embed_scale"] = em         # Granite layout: gather and scale in one launch (_embed)
@@ -1477,6 +1533,10 @@ def accelerate_llm(model: nn.Module, linears: bool = True, fuse: bool = True, la
             # static caches beyond ATTN_MAXLEN slots stay fused up to this many (the key-split attention entries); longer ones run HF's layers
             info["long_cache_attention_max_slots"] = ATTN_SPLIT_MAXLEN
             n_moe = sum(isinstance(l.__dict__.get("_ll_fused"), _FusedMoeLayer) for l in all_layers)
+            n_win = sum(getattr(l.__dict__.get("_ll_fused"), "window", None) is not None for l in all_layers)
+            if n_win:
+                # of the fused layers, the sliding-window ones: the windowed key-split attention wherever the cache is longer than the window
+                info["sliding_window_layers_fused"] = n_win
             if n_moe:
                 # of the fused layers, the ones whose MLP half is the MoE calls (eight launches at 1..16 rows; the key above counts them too)
                 info["moe_layers_fused"] = n_moe

@@ -250,7 +250,6 @@ class GraphedDecoder:
 
     # static buffers + captured step for a (batch, max_len) shape
     def _prepare(self, B: int, max_len: int, device, use_embeds: bool):
-        from transformers import StaticCache
         key = (B, max_len, use_embeds)
         if self._key == key:
             self.cache.reset()
@@ -262,7 +261,9 @@ class GraphedDecoder:
             on_device = torch.device(device).type == "cuda"
             self.cache = MX8StaticCache(cfg, B, max_len, device, torch.bfloat16 if on_device else next(self.model.parameters()).dtype)
         else:
-            self.cache = StaticCache(config=cfg, max_cache_len=max_len)
+            # (a config with sliding-window layers gets full-length layers: HF's sliding cache layer branches on the host, kv_cache.py)
+            from .kv_cache import static_cache_for
+            self.cache = static_cache_for(cfg, max_len)
         self.tok = torch.zeros(B, 1, dtype=torch.long, device=device)
         self.pos = torch.zeros(1, dtype=torch.long, device=device)
         self.mask = torch.zeros(B, max_len, dtype=torch.long, device=device)
