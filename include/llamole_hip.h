@@ -638,6 +638,38 @@ int ll_moe_experts_bf16(const void *x, int ldx, const void *norm_w, float eps, c
                         const void *Wd, const void *residual, int ldr, void *out, int ldo, int M, int E, int top_k, int H, int I,
                         void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- the same block in the Mixtral and the shared-expert (Qwen2-MoE) layouts ----------------------------------------------------------
+ * MixtralSparseMoeBlock (transformers modeling_mixtral.py) and Qwen2MoeSparseMoeBlock (modeling_qwen2_moe.py) keep the parts above -- experts
+ * as gate_up_proj [E, 2I, H] / down_proj [E, H, I], a router weight [E, H], SiLU, no biases -- and differ from the Qwen3 contract in two pieces
+ * of arithmetic.  Bounds, workspace (ll_moe_workspace_bytes, unchanged), stream behaviour and launch counts are those of the calls above.
+ *
+ * ll_moe_route_f32 : ll_moe_route_bf16 with w [M, top_k] written as FLOAT, the f32 value itself, never rounded to bf16 (MixtralTopKRouter keeps
+ *     its renormalised weights in f32; it always renormalises: pass norm_topk = 1).  Selection, tie rule, grouping and workspace layout are
+ *     those of ll_moe_route_bf16.
+ *
+ * ll_moe_experts_ex_bf16 : ll_moe_experts_bf16 with two options; with both off (w_f32 == 0, shared == NULL) it IS that call, bit for bit.
+ *   w_f32 != 0 (Mixtral): w is the float [M, top_k] of ll_moe_route_f32.  The down launch stores the unweighted y_mj where z_mj stood and
+ *     the slot sum applies the weight:
+ *         y_mj  = bf16( a_mj . Wd[e]^T )
+ *         out_m = bf16( float(residual_m) + float( bf16( sum_j f32( w_mj * float(y_mj) ) ) ) )
+ *     every product rounded to f32 on its own (no fused multiply-add), the sum in f32 in slot order, ONE rounding to bf16: HF's default
+ *     experts path on f32 weights (bf16 * f32 -> f32, view(tokens, k, H).sum(dim=1), one cast).  No per-slot rounding z_mj = bf16(w y).
+ *   shared != NULL (Qwen2-MoE): shared [M, H] bf16 (row stride lds elements, a multiple of 8, 16-byte aligned) holds the shared expert's
+ *     output s_m = shared_expert(rmsnorm(x_m)) -- computed by the caller with the dense MLP's own kernels (ll_gemv_fused_bf16 /
+ *     ll_linear_rows16_bf16 / ll_linear_rows64_bf16: gate|up with the RMSNorm prologue and the SiLU*mul epilogue, down with the plain one) --
+ *     and gate[m * ldg] (bf16, any ldg >= 1: a column of a wider matrix) the logit g_m = bf16(rmsnorm(x_m) . shared_expert_gate.weight[0]).
+ *     With e_m = bf16(sum_j z_mj) (or the w_f32 sum above):
+ *         sig_m = bf16( 1 / (1 + exp(-float(g_m))) )                                             f32 evaluation
+ *         out_m = bf16( float(residual_m) + float( bf16( float(e_m) + float( bf16( float(sig_m) * float(s_m) ) ) ) ) )
+ *     i.e. F.sigmoid(shared_expert_gate(x)) * shared_expert(x) added to the experts' output, then the layer's residual add, each a bf16 tensor
+ *     operation of HF's forward.
+ *   Three launches, as ll_moe_experts_bf16.  A bound violated returns LL_EINVAL and launches nothing. */
+int ll_moe_route_f32(const void *logits, int ld, int M, int E, int top_k, int norm_topk, int32_t *idx, float *w, void *workspace,
+                     int64_t workspace_bytes, void *stream);
+int ll_moe_experts_ex_bf16(const void *x, int ldx, const void *norm_w, float eps, const int32_t *idx, const void *w, int w_f32, const void *Wgu,
+                           const void *Wd, const void *residual, int ldr, const void *shared, int lds, const void *gate, int ldg, void *out,
+                           int ldo, int M, int E, int top_k, int H, int I, void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,8 @@ SIGNATURES = {
     "ll_moe_workspace_bytes": (_I64, [_I, _I, _I, _I, _I]),
     "ll_moe_route_bf16": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _I64, _P]),
     "ll_moe_experts_bf16": (_I, [_P, _I, _P, _F, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I64, _P]),
+    "ll_moe_route_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _I64, _P]),
+    "ll_moe_experts_ex_bf16": (_I, [_P, _I, _P, _F, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I64, _P]),
 }
 
 # include/llamole_hip_tuning.h: exported by libllamole_hip_tuning.so only (the LL_TUNING=1 build of the same sources)

@@ -7,6 +7,9 @@
 //                        blockIdx.y is a slot of the active-expert list (min(E, M*top_k) slots; slots past the list exit at once), and the
 //                        workgroups of one expert take all of its token rows in passes of up to 4 rows over their weight tile, so an expert's
 //                        matrices come from HBM once per launch (later passes re-read the tile from L2), not once per (row, slot) pair.
+//   ll_moe_route_f32 / ll_moe_experts_ex_bf16  the Mixtral and Qwen2-MoE layouts as compile-time variants of the same kernels: routing weights
+//                        stored and applied in f32 (the down launch then stores the unweighted projection and the slot sum multiplies), and a
+//                        sigmoid-gated shared expert added in the slot sum; with both options off the entry IS ll_moe_experts_bf16.
 // The GEMV arithmetic is gemv_fused_body (gemv_body.h), the body of the dense ll_gemv_fused_bf16: a row that is alone on its expert is
 // rounded bit for bit like the dense kernel on that expert's matrices.  No floating-point atomics; every sum has a fixed order.
 // Workspace (private layout), for P = M * top_k pairs and A = min(E, P) active-expert slots:
@@ -34,8 +37,10 @@ __device__ __forceinline__ void route_better(float &bv, int &bi, float v, int i)
 }
 
 // One workgroup of 4 waves; wave w routes rows w, w + 4, ...; a lane holds logits lane, lane + 64, lane + 128, lane + 192 of its row.
+// WF32 (ll_moe_route_f32, the Mixtral router): the weights leave as the f32 values themselves, never rounded to bf16.
+template <bool WF32 = false>
 __global__ __launch_bounds__(256) void moe_route_kernel(const bf16_t *__restrict__ logits, int ld, int M, int E, int top_k, int norm_topk,
-                                                        int *__restrict__ idx, bf16_t *__restrict__ wout, int *__restrict__ ws) {
+                                                        int *__restrict__ idx, void *__restrict__ wout, int *__restrict__ ws) {
     __shared__ int sidx[512];      // expert of pair m * top_k + j
     __shared__ int cnt[256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -94,7 +99,9 @@ __global__ __launch_bounds__(256) void moe_route_kernel(const bf16_t *__restrict
                     const int e = min(max(seli[j], 0), E - 1);
                     idx[m * top_k + j] = e;
                     sidx[m * top_k + j] = e;
-                    wout[m * top_k + j] = f32_to_bf16(norm_topk ? p[j] / ps : p[j]);
+                    const float wj = norm_topk ? p[j] / ps : p[j];
+                    if (WF32) reinterpret_cast<float *>(wout)[m * top_k + j] = wj;
+                    else reinterpret_cast<bf16_t *>(wout)[m * top_k + j] = f32_to_bf16(wj);
                 }
         }
     }
@@ -145,8 +152,9 @@ __device__ __forceinline__ bool moe_group(const int *__restrict__ ws, const int 
 }
 
 // One pass of R (1..4) token rows of the group over this workgroup's weight tile.  GU: gate|up (RMSNorm prologue on the rows of x the pairs
-// belong to, SiLU*mul epilogue -> act[pair]); otherwise down (x = act[pair], epilogue bf16(bf16(acc) * w[pair]) -> z[pair]).
-template <int R, bool GU, bool NT, int XC>
+// belong to, SiLU*mul epilogue -> act[pair]); otherwise down (x = act[pair], epilogue bf16(bf16(acc) * w[pair]) -> z[pair]; YRAW: the plain
+// epilogue bf16(acc) -> z[pair], the routing weight is not read -- ll_moe_experts_ex_bf16 with f32 weights applies it in the slot sum).
+template <int R, bool GU, bool NT, int XC, bool YRAW = false>
 __device__ __forceinline__ void moe_pass(const int *__restrict__ pair, int P, int top_k, const bf16_t *__restrict__ X, int ldx,
                                          const bf16_t *__restrict__ normw, float eps, const bf16_t *__restrict__ W,
                                          const bf16_t *__restrict__ rw, bf16_t *__restrict__ outp, int N, int K, bf16_t *xs, float (*red)[4]) {
@@ -159,9 +167,9 @@ __device__ __forceinline__ void moe_pass(const int *__restrict__ pair, int P, in
         xr[r] = GU ? X + (int64_t)(q / top_k) * ldx : X + (int64_t)q * ldx;
         rr[r] = nullptr;
         cr[r] = outp + (int64_t)q * N;
-        rs[r] = GU ? 1.f : bf16_to_f32(rw[q]);
+        rs[r] = (GU || YRAW) ? 1.f : bf16_to_f32(rw[q]);
     }
-    gemv_fused_body<R, GU, GU ? GEMV_SILU_MUL : GEMV_SCALE, NT, XC>(xr, W, K, nullptr, normw, eps, rr, cr, rs, N, K,
+    gemv_fused_body<R, GU, GU ? GEMV_SILU_MUL : (YRAW ? GEMV_PLAIN : GEMV_SCALE), NT, XC>(xr, W, K, nullptr, normw, eps, rr, cr, rs, N, K,
                                                                    blockIdx.x * 4 + (threadIdx.x >> 6), xs, red);
 }
 
@@ -170,7 +178,7 @@ __device__ __forceinline__ void moe_pass(const int *__restrict__ pair, int P, in
 // decode step thus runs the one-row body at the dense GEMV's register count, not at the four-row body's.  Earlier passes of a group load
 // the tile with ordinary loads (it is read again), the last pass with non-temporal ones (the dense GEMV's choice for a matrix that is
 // streamed once).
-template <bool GU, int XC, int MAXR, bool MULTI>
+template <bool GU, int XC, int MAXR, bool MULTI, bool YRAW = false>
 __global__ __launch_bounds__(256) void moe_expert_kernel(const bf16_t *__restrict__ X, int ldx, const bf16_t *__restrict__ normw, float eps,
                                                          const int *__restrict__ idx, const bf16_t *__restrict__ rw,
                                                          const bf16_t *__restrict__ Wall, const int *__restrict__ ws,
@@ -187,7 +195,7 @@ __global__ __launch_bounds__(256) void moe_expert_kernel(const bf16_t *__restric
     for (int p0 = g.beg; p0 < g.end; p0 += 4) {
         if (MULTI && p0 > g.beg) __syncthreads();      // xs / red of the previous pass are free
         const int n = g.end - p0;
-#define LL_MOE_PASS(R_, NT_) moe_pass<R_, GU, NT_, XC>(pair + p0, P, top_k, X, ldx, normw, eps, W, rw, outp, N, K, xs, red)
+#define LL_MOE_PASS(R_, NT_) moe_pass<R_, GU, NT_, XC, YRAW>(pair + p0, P, top_k, X, ldx, normw, eps, W, rw, outp, N, K, xs, red)
         if (MULTI && n > 4) LL_MOE_PASS(4, false);
         else if (MAXR >= 4 && n >= 4) LL_MOE_PASS(4, true);
         else if (MAXR >= 3 && n == 3) LL_MOE_PASS(3, true);
@@ -197,11 +205,11 @@ __global__ __launch_bounds__(256) void moe_expert_kernel(const bf16_t *__restric
     }
 }
 
-template <bool GU, int XC>
+template <bool GU, int XC, bool YRAW = false>
 static void launch_moe_expert(int M, dim3 grid, size_t lds, hipStream_t s, const bf16_t *X, int ldx, const bf16_t *normw, float eps,
                               const int *idx, const bf16_t *rw, const bf16_t *Wall, const int *ws, bf16_t *outp, int P, int A, int E, int top_k,
                               int N, int K, int64_t wstride) {
-#define LL_MOE_K(MAXR_, MULTI_) hipLaunchKernelGGL((moe_expert_kernel<GU, XC, MAXR_, MULTI_>), grid, dim3(256), lds, s, X, ldx, normw, eps, idx, rw, \
+#define LL_MOE_K(MAXR_, MULTI_) hipLaunchKernelGGL((moe_expert_kernel<GU, XC, MAXR_, MULTI_, YRAW>), grid, dim3(256), lds, s, X, ldx, normw, eps, idx, rw, \
                                                    Wall, ws, outp, P, A, E, top_k, N, K, wstride)
     if (M == 1) LL_MOE_K(1, false);
     else if (M == 2) LL_MOE_K(2, false);
@@ -236,6 +244,59 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(const bf16_t *__restri
     }
 }
 
+// The slot sum of ll_moe_experts_ex_bf16.  grid M.
+//   WF32:   z holds the unweighted y; the sum is sum_j f32(w[m, j] * float(y_mj)) with w in f32 -- every product rounded to f32 on its own
+//           (no fused multiply-add), added in slot order, ONE rounding to bf16;  otherwise the sum of moe_combine_kernel.
+//   SHARED: out = bf16(res + bf16(float(bf16(sum)) + float(bf16(float(sig) * float(s))))),  sig = bf16(1 / (1 + exp(-float(g[m * ldg])))).
+template <bool WF32, bool SHARED>
+__global__ __launch_bounds__(256) void moe_combine_ex_kernel(const bf16_t *__restrict__ z, const void *__restrict__ wv,
+                                                             const bf16_t *__restrict__ res, int ldr, const bf16_t *__restrict__ sh, int lds,
+                                                             const bf16_t *__restrict__ gate, int ldg, bf16_t *__restrict__ out, int ldo,
+                                                             int top_k, int H) {
+    const int m = blockIdx.x;
+    float wj[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) wj[j] = (WF32 && j < top_k) ? reinterpret_cast<const float *>(wv)[m * top_k + j] : 0.f;
+    float sig = 0.f;
+    if (SHARED) sig = bfr2(1.f / (1.f + expf(-bf16_to_f32(gate[(int64_t)m * ldg]))));
+    for (int ch = threadIdx.x; ch < H / 8; ch += 256) {
+        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (j < top_k) {
+                const u32x4 v = *reinterpret_cast<const u32x4 *>(z + ((int64_t)m * top_k + j) * H + ch * 8);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const float a = __uint_as_float(v[t] << 16), b = __uint_as_float(v[t] & 0xffff0000u);
+                    if (WF32) {
+                        acc[2 * t] = __fadd_rn(acc[2 * t], __fmul_rn(wj[j], a));
+                        acc[2 * t + 1] = __fadd_rn(acc[2 * t + 1], __fmul_rn(wj[j], b));
+                    } else {
+                        acc[2 * t] += a;
+                        acc[2 * t + 1] += b;
+                    }
+                }
+            }
+        }
+        if (SHARED) {
+            const u32x4 sv = *reinterpret_cast<const u32x4 *>(sh + (int64_t)m * lds + ch * 8);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                acc[2 * t] = __fadd_rn(bfr2(acc[2 * t]), bfr2(__fmul_rn(sig, __uint_as_float(sv[t] << 16))));
+                acc[2 * t + 1] = __fadd_rn(bfr2(acc[2 * t + 1]), bfr2(__fmul_rn(sig, __uint_as_float(sv[t] & 0xffff0000u))));
+            }
+        }
+        const u32x4 r = *reinterpret_cast<const u32x4 *>(res + (int64_t)m * ldr + ch * 8);
+        u32x4 o;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float a = __uint_as_float(r[t] << 16) + bfr2(acc[2 * t]), b = __uint_as_float(r[t] & 0xffff0000u) + bfr2(acc[2 * t + 1]);
+            o[t] = (uint32_t)f32_to_bf16(a) | ((uint32_t)f32_to_bf16(b) << 16);
+        }
+        *reinterpret_cast<u32x4 *>(out + (int64_t)m * ldo + ch * 8) = o;
+    }
+}
+
 }  // namespace ll
 
 using namespace ll;
@@ -247,6 +308,19 @@ int64_t ll_moe_workspace_bytes(int M, int E, int top_k, int H, int I) {
     return moe_int_bytes(M, E, top_k) + (int64_t)M * top_k * ((int64_t)I + H) * 2;
 }
 
+int ll_moe_route_f32(const void *logits, int ld, int M, int E, int top_k, int norm_topk, int32_t *idx, float *w, void *workspace,
+                     int64_t workspace_bytes, void *stream) {
+    LL_CHECK(logits && idx && w && workspace, "ll_moe_route_f32: null argument");
+    LL_CHECK(moe_route_shape_ok(M, E, top_k), "ll_moe_route_f32: M=%d rows (1..64), E=%d experts (<= 256), top_k=%d (1..min(E, 8))", M, E, top_k);
+    LL_CHECK(ld >= E, "ll_moe_route_f32: row stride %d < E", ld);
+    LL_CHECK(workspace_bytes >= moe_int_bytes(M, E, top_k) && ((uintptr_t)workspace & 15) == 0,
+             "ll_moe_route_f32: workspace too small or not 16-byte aligned (ll_moe_workspace_bytes)");
+    hipLaunchKernelGGL(moe_route_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, (const bf16_t *)logits, ld, M, E, top_k, norm_topk,
+                       (int *)idx, (void *)w, (int *)workspace);
+    LL_LAUNCH_CHECK();
+    return LL_OK;
+}
+
 int ll_moe_route_bf16(const void *logits, int ld, int M, int E, int top_k, int norm_topk, int32_t *idx, void *w, void *workspace,
                       int64_t workspace_bytes, void *stream) {
     LL_CHECK(logits && idx && w && workspace, "ll_moe_route_bf16: null argument");
@@ -254,43 +328,95 @@ int ll_moe_route_bf16(const void *logits, int ld, int M, int E, int top_k, int n
     LL_CHECK(ld >= E, "ll_moe_route_bf16: row stride %d < E", ld);
     LL_CHECK(workspace_bytes >= moe_int_bytes(M, E, top_k) && ((uintptr_t)workspace & 15) == 0,
              "ll_moe_route_bf16: workspace too small or not 16-byte aligned (ll_moe_workspace_bytes)");
-    hipLaunchKernelGGL(moe_route_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const bf16_t *)logits, ld, M, E, top_k, norm_topk,
-                       (int *)idx, (bf16_t *)w, (int *)workspace);
+    hipLaunchKernelGGL(moe_route_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, (const bf16_t *)logits, ld, M, E, top_k, norm_topk,
+                       (int *)idx, w, (int *)workspace);
     LL_LAUNCH_CHECK();
     return LL_OK;
+}
+
+// The bounds ll_moe_experts_bf16 and ll_moe_experts_ex_bf16 share; `fn` names the entry in the message.
+static int moe_experts_check(const char *fn, const void *x, int ldx, const void *norm_w, float eps, const int32_t *idx, const void *w, const void *Wgu,
+                             const void *Wd, const void *residual, int ldr, const void *out, int ldo, int M, int E, int top_k, int H, int I,
+                             const void *workspace, int64_t workspace_bytes) {
+    LL_CHECK(x && norm_w && idx && w && Wgu && Wd && residual && out && workspace, "%s: null argument", fn);
+    LL_CHECK(moe_route_shape_ok(M, E, top_k), "%s: M=%d rows (1..64), E=%d experts (<= 256), top_k=%d (1..min(E, 8))", fn, M, E, top_k);
+    LL_CHECK(H >= 8 && H % 8 == 0 && H <= 8192 && I >= 8 && I % 8 == 0 && I <= 32768, "%s: H=%d (multiple of 8 up to 8192), I=%d (multiple of 8 up to 32768)", fn, H, I);
+    LL_CHECK(ldx >= H && ldr >= H && ldo >= H && ldx % 8 == 0 && ldr % 8 == 0 && ldo % 8 == 0, "%s: row strides must be multiples of 8, at least H", fn);
+    LL_CHECK(eps > 0.f, "%s: eps must be positive", fn);
+    LL_CHECK(workspace_bytes >= ll_moe_workspace_bytes(M, E, top_k, H, I) && ((uintptr_t)workspace & 15) == 0,
+             "%s: workspace too small or not 16-byte aligned (ll_moe_workspace_bytes)", fn);
+    LL_CHECK((((uintptr_t)x | (uintptr_t)norm_w | (uintptr_t)Wgu | (uintptr_t)Wd | (uintptr_t)residual | (uintptr_t)out) & 15) == 0,
+             "%s: operands must be 16-byte aligned", fn);
+    return LL_OK;
+}
+
+// The gate|up launch of both entries: act[pair] = SiLU(gate) * up over the active experts (the routing weights are not read).
+static void moe_launch_gate_up(int M, hipStream_t s, const void *x, int ldx, const void *norm_w, float eps, const int32_t *idx, const void *Wgu,
+                               const int *ws, bf16_t *act, int E, int top_k, int H, int I) {
+    const int P = M * top_k, A = E < P ? E : P;
+    const size_t lds = (size_t)(M < 4 ? M : 4) * H * 2;
+    const dim3 g1(cdiv(I, 4), A);
+    if (H <= 4096)
+        launch_moe_expert<true, 2>(M, g1, lds, s, (const bf16_t *)x, ldx, (const bf16_t *)norm_w, eps, (const int *)idx, nullptr,
+                                   (const bf16_t *)Wgu, ws, act, P, A, E, top_k, I, H, (int64_t)2 * I * H);
+    else
+        launch_moe_expert<true, 4>(M, g1, lds, s, (const bf16_t *)x, ldx, (const bf16_t *)norm_w, eps, (const int *)idx, nullptr,
+                                   (const bf16_t *)Wgu, ws, act, P, A, E, top_k, I, H, (int64_t)2 * I * H);
 }
 
 int ll_moe_experts_bf16(const void *x, int ldx, const void *norm_w, float eps, const int32_t *idx, const void *w, const void *Wgu,
                         const void *Wd, const void *residual, int ldr, void *out, int ldo, int M, int E, int top_k, int H, int I,
                         void *workspace, int64_t workspace_bytes, void *stream) {
-    LL_CHECK(x && norm_w && idx && w && Wgu && Wd && residual && out && workspace, "ll_moe_experts_bf16: null argument");
-    LL_CHECK(moe_route_shape_ok(M, E, top_k), "ll_moe_experts_bf16: M=%d rows (1..64), E=%d experts (<= 256), top_k=%d (1..min(E, 8))", M, E, top_k);
-    LL_CHECK(H >= 8 && H % 8 == 0 && H <= 8192 && I >= 8 && I % 8 == 0 && I <= 32768, "ll_moe_experts_bf16: H=%d (multiple of 8 up to 8192), I=%d (multiple of 8 up to 32768)", H, I);
-    LL_CHECK(ldx >= H && ldr >= H && ldo >= H && ldx % 8 == 0 && ldr % 8 == 0 && ldo % 8 == 0, "ll_moe_experts_bf16: row strides must be multiples of 8, at least H");
-    LL_CHECK(eps > 0.f, "ll_moe_experts_bf16: eps must be positive");
-    LL_CHECK(workspace_bytes >= ll_moe_workspace_bytes(M, E, top_k, H, I) && ((uintptr_t)workspace & 15) == 0,
-             "ll_moe_experts_bf16: workspace too small or not 16-byte aligned (ll_moe_workspace_bytes)");
-    LL_CHECK((((uintptr_t)x | (uintptr_t)norm_w | (uintptr_t)Wgu | (uintptr_t)Wd | (uintptr_t)residual | (uintptr_t)out) & 15) == 0,
-             "ll_moe_experts_bf16: operands must be 16-byte aligned");
+    LL_TRY(moe_experts_check("ll_moe_experts_bf16", x, ldx, norm_w, eps, idx, w, Wgu, Wd, residual, ldr, out, ldo, M, E, top_k, H, I, workspace,
+                             workspace_bytes));
     const int P = M * top_k, A = E < P ? E : P;
     const int *ws = (const int *)workspace;
     bf16_t *act = (bf16_t *)((char *)workspace + moe_int_bytes(M, E, top_k));
     bf16_t *z = act + (int64_t)P * I;
     hipStream_t s = (hipStream_t)stream;
-    const bf16_t *X = (const bf16_t *)x, *nw = (const bf16_t *)norm_w, *rw = (const bf16_t *)w;
-    const size_t lds = (size_t)(M < 4 ? M : 4) * H * 2;
-    const dim3 g1(cdiv(I, 4), A), g2(cdiv(H, 8), A);
-    if (H <= 4096)
-        launch_moe_expert<true, 2>(M, g1, lds, s, X, ldx, nw, eps, (const int *)idx, rw, (const bf16_t *)Wgu, ws, act, P, A, E, top_k, I, H,
-                                   (int64_t)2 * I * H);
-    else
-        launch_moe_expert<true, 4>(M, g1, lds, s, X, ldx, nw, eps, (const int *)idx, rw, (const bf16_t *)Wgu, ws, act, P, A, E, top_k, I, H,
-                                   (int64_t)2 * I * H);
+    moe_launch_gate_up(M, s, x, ldx, norm_w, eps, idx, Wgu, ws, act, E, top_k, H, I);
     LL_LAUNCH_CHECK();
-    launch_moe_expert<false, 2>(M, g2, 0, s, (const bf16_t *)act, I, nullptr, 0.f, (const int *)idx, rw, (const bf16_t *)Wd, ws, z, P, A, E, top_k,
-                                H, I, (int64_t)H * I);
+    launch_moe_expert<false, 2>(M, dim3(cdiv(H, 8), A), 0, s, (const bf16_t *)act, I, nullptr, 0.f, (const int *)idx, (const bf16_t *)w,
+                                (const bf16_t *)Wd, ws, z, P, A, E, top_k, H, I, (int64_t)H * I);
     LL_LAUNCH_CHECK();
     hipLaunchKernelGGL(moe_combine_kernel, dim3(M), dim3(256), 0, s, (const bf16_t *)z, (const bf16_t *)residual, ldr, (bf16_t *)out, ldo, top_k, H);
+    LL_LAUNCH_CHECK();
+    return LL_OK;
+}
+
+int ll_moe_experts_ex_bf16(const void *x, int ldx, const void *norm_w, float eps, const int32_t *idx, const void *w, int w_f32, const void *Wgu,
+                           const void *Wd, const void *residual, int ldr, const void *shared, int lds, const void *gate, int ldg, void *out,
+                           int ldo, int M, int E, int top_k, int H, int I, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (!w_f32 && !shared)      // both options off: the call it extends, bit for bit
+        return ll_moe_experts_bf16(x, ldx, norm_w, eps, idx, w, Wgu, Wd, residual, ldr, out, ldo, M, E, top_k, H, I, workspace, workspace_bytes,
+                                   stream);
+    LL_TRY(moe_experts_check("ll_moe_experts_ex_bf16", x, ldx, norm_w, eps, idx, w, Wgu, Wd, residual, ldr, out, ldo, M, E, top_k, H, I, workspace,
+                             workspace_bytes));
+    LL_CHECK(!w_f32 || ((uintptr_t)w & 3) == 0, "ll_moe_experts_ex_bf16: f32 routing weights must be 4-byte aligned");
+    LL_CHECK(!shared || (gate && lds >= H && lds % 8 == 0 && ldg >= 1 && ((uintptr_t)shared & 15) == 0 && ((uintptr_t)gate & 1) == 0),
+             "ll_moe_experts_ex_bf16: the shared expert's rows need a gate column, a row stride that is a multiple of 8, at least H, and 16-byte alignment");
+    const int P = M * top_k, A = E < P ? E : P;
+    const int *ws = (const int *)workspace;
+    bf16_t *act = (bf16_t *)((char *)workspace + moe_int_bytes(M, E, top_k));
+    bf16_t *z = act + (int64_t)P * I;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 g2(cdiv(H, 8), A);
+    moe_launch_gate_up(M, s, x, ldx, norm_w, eps, idx, Wgu, ws, act, E, top_k, H, I);
+    LL_LAUNCH_CHECK();
+    if (w_f32)      // the unweighted projection: the f32 weights are read by the slot sum only
+        launch_moe_expert<false, 2, true>(M, g2, 0, s, (const bf16_t *)act, I, nullptr, 0.f, (const int *)idx, nullptr, (const bf16_t *)Wd, ws, z, P, A,
+                                          E, top_k, H, I, (int64_t)H * I);
+    else
+        launch_moe_expert<false, 2>(M, g2, 0, s, (const bf16_t *)act, I, nullptr, 0.f, (const int *)idx, (const bf16_t *)w, (const bf16_t *)Wd, ws, z, P,
+                                    A, E, top_k, H, I, (int64_t)H * I);
+    LL_LAUNCH_CHECK();
+#define LL_MOE_COMBINE(WF32_, SHARED_) hipLaunchKernelGGL((moe_combine_ex_kernel<WF32_, SHARED_>), dim3(M), dim3(256), 0, s, (const bf16_t *)z, w, \
+                                                          (const bf16_t *)residual, ldr, (const bf16_t *)shared, lds, (const bf16_t *)gate, ldg,  \
+                                                          (bf16_t *)out, ldo, top_k, H)
+    if (w_f32 && shared) LL_MOE_COMBINE(true, true);
+    else if (w_f32) LL_MOE_COMBINE(true, false);
+    else LL_MOE_COMBINE(false, true);
+#undef LL_MOE_COMBINE
     LL_LAUNCH_CHECK();
     return LL_OK;
 }

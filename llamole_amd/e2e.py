@@ -75,6 +75,24 @@ LLM_CONFIGS = {
     "tiny-qwen2-sw": dict(cls="Qwen2", hidden_size=256, num_hidden_layers=2, num_attention_heads=4, num_key_value_heads=2,
                           intermediate_size=512, vocab_size=2048, max_position_embeddings=2048, rope_theta=10000.0,
                           rms_norm_eps=1e-6, tie_word_embeddings=False, use_sliding_window=True, sliding_window=24, max_window_layers=1),
+    # Mixtral layout: the Mistral attention with a sparse-MoE MLP whose router keeps its renormalised weights in f32.  Qwen2-MoE layout: the Qwen2
+    # attention (q/k/v bias), the Qwen3-MoE routing and a sigmoid-gated shared expert next to the routed ones; a mixed model is
+    # build_llm("tiny-qwen2-moe", ..., mlp_only_layers=[0]).  The widths of "mixtral-8x7b" and "qwen1.5-moe-a2.7b" are written from memory of the
+    # published mistralai/Mixtral-8x7B-v0.1 and Qwen/Qwen1.5-MoE-A2.7B config.json files, not read from them
+    "mixtral-8x7b": dict(cls="Mixtral", hidden_size=4096, num_hidden_layers=32, num_attention_heads=32, num_key_value_heads=8,
+                         intermediate_size=14336, num_local_experts=8, num_experts_per_tok=2, vocab_size=32000, max_position_embeddings=32768,
+                         rope_theta=1000000.0, rms_norm_eps=1e-5, sliding_window=None, tie_word_embeddings=False),
+    "tiny-mixtral": dict(cls="Mixtral", hidden_size=256, num_hidden_layers=2, num_attention_heads=4, num_key_value_heads=2,
+                         intermediate_size=512, num_local_experts=8, num_experts_per_tok=2, vocab_size=2048, max_position_embeddings=2048,
+                         rope_theta=10000.0, rms_norm_eps=1e-5, sliding_window=None, tie_word_embeddings=False),
+    "qwen1.5-moe-a2.7b": dict(cls="Qwen2Moe", hidden_size=2048, num_hidden_layers=24, num_attention_heads=16, num_key_value_heads=16,
+                              num_experts=60, num_experts_per_tok=4, moe_intermediate_size=1408, shared_expert_intermediate_size=5632,
+                              intermediate_size=5632, vocab_size=151936, max_position_embeddings=8192, rope_theta=1000000.0, rms_norm_eps=1e-6,
+                              norm_topk_prob=False, decoder_sparse_step=1, mlp_only_layers=[], tie_word_embeddings=False),
+    "tiny-qwen2-moe": dict(cls="Qwen2Moe", hidden_size=256, num_hidden_layers=2, num_attention_heads=4, num_key_value_heads=2,
+                           num_experts=8, num_experts_per_tok=2, moe_intermediate_size=128, shared_expert_intermediate_size=384,
+                           intermediate_size=512, vocab_size=2048, max_position_embeddings=2048, rope_theta=10000.0, rms_norm_eps=1e-6,
+                           norm_topk_prob=False, decoder_sparse_step=1, mlp_only_layers=[], tie_word_embeddings=False),
 }
 
 # rope_parameters of the published meta-llama/Meta-Llama-3.1-8B-Instruct config.json (rope_scaling there): the "llama-3.1-8b" entry above has the

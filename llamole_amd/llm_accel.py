@@ -261,6 +261,13 @@ def refresh_weight_copies(model: nn.Module) -> int:
                     d["_ll_gate_up"].copy_(torch.cat([mod.gate_proj.weight.detach(), mod.up_proj.weight.detach()], dim=0))
                     d["_ll_gate_up_key"] = key
                     n += 1
+            if "_ll_router_gate" in d and isinstance(getattr(mod, "shared_expert_gate", None), nn.Module):
+                # a shared-expert MoE block: the stacked [E + 1, H] copy of the router and the shared gate (_FusedMoeLayer)
+                key = _versions(mod.gate.weight, mod.shared_expert_gate.weight)
+                if d.get("_ll_router_gate_key") != key:
+                    d["_ll_router_gate"].copy_(torch.cat([mod.gate.weight.detach(), mod.shared_expert_gate.weight.detach()], dim=0))
+                    d["_ll_router_gate_key"] = key
+                    n += 1
             if "_ll_bias_f32" in d and getattr(mod, "bias", None) is not None:
                 key = _versions(mod.bias)
                 if d.get("_ll_bias_key") != key:
@@ -290,7 +297,7 @@ def refresh_weight_copies(model: nn.Module) -> int:
 def drop_weight_copies(model: nn.Module) -> None:
     """Forget the concatenated / converted weight copies (restore_* paths): the next install rebuilds them."""
     for mod in model.modules():
-        for k in ("_ll_gate_up", "_ll_gate_up_key", "_ll_bias_f32", "_ll_bias_key", "_ll_qkv", "_ll_w64"):
+        for k in ("_ll_gate_up", "_ll_gate_up_key", "_ll_bias_f32", "_ll_bias_key", "_ll_qkv", "_ll_w64", "_ll_router_gate", "_ll_router_gate_key"):
             mod.__dict__.pop(k, None)
 
 
@@ -741,11 +748,14 @@ class _FusedLayer:
         q, k, v, o, g, u, d = self._mods
         return (_versions(q.weight, k.weight, v.weight), _versions(o.weight), _versions(g.weight, u.weight), _versions(d.weight))
 
+    def _packed64_sources(self):
+        """(matrices, keys) of the rows64 copies: the matrices of ``_srcs`` (a layer with a shared expert adds that expert's, which get no MX codes)."""
+        return self._srcs(), self._keys64()
+
     def packed64(self, sync: bool = False):
         """[q|k|v], o_proj, [gate|up], down_proj in MFMA operand order (ll_rows64_pack_bf16) -- one more copy of the layer's weights,
         made the first time 17..64 sequences are decoded together; ``sync`` re-packs in place what changed at the source."""
-        keys = self._keys64()
-        srcs = self._srcs()
+        srcs, keys = self._packed64_sources()
         if self.p64 is None:
             self.p64 = tuple(_Packed64(self.lib, w, key) for w, key in zip(srcs, keys))
         elif sync:
@@ -996,7 +1006,12 @@ class _FusedMoeLayer(_FusedLayer):
     parent's; the MLP half is router logits (the dense Linear on mlp.gate.weight with the post-attention RMSNorm as prologue), ll_moe_route_bf16
     and ll_moe_experts_bf16 (gate|up, down, slot sum + residual) -- eight launches per layer at 1..16 rows.  The expert and router parameters
     are read in place: no copy, nothing for ``refresh_weight_copies`` to follow.  ``idx`` / ``w`` keep the routing of the latest call (static
-    buffers: a captured graph rewrites them at every replay)."""
+    buffers: a captured graph rewrites them at every replay).
+    Mixtral layout (``w_f32``): the routing weights stay f32 (ll_moe_route_f32) and the slot sum applies them (ll_moe_experts_ex_bf16) -- eight
+    launches as well.  Qwen2-MoE layout (``shared``): the router Linear runs over a stacked [E + 1, H] copy of gate.weight and
+    shared_expert_gate.weight (column E of its output is the shared gate's logit; the copy follows its sources in
+    ``refresh_weight_copies``), the shared expert is the dense MLP's gate|up and down launches on its own concatenated copy, and the slot sum
+    adds sigmoid(gate) * shared -- ten launches."""
 
     def __init__(self, lib, layer, workspaces: dict, split_ws: Optional[dict] = None):
         self._workspaces = workspaces
@@ -1006,17 +1021,33 @@ class _FusedMoeLayer(_FusedLayer):
         mlp = layer.mlp
         self.experts, self.router = mlp.experts, mlp.gate
         self.E, _, self.I = (int(v) for v in mlp.experts.down_proj.shape)
-        self.top_k, self.norm_topk = int(mlp.gate.top_k), bool(mlp.gate.norm_topk_prob)
+        family = _moe_family(mlp)
+        self.w_f32 = family == "mixtral"          # MixtralTopKRouter: f32 weights, always renormalised
+        self.top_k, self.norm_topk = int(mlp.gate.top_k), True if self.w_f32 else bool(mlp.gate.norm_topk_prob)
         self.stream_ok = self.H % 32 == 0 and self.nq % 32 == 0 and self.n1.weight.dtype == torch.bfloat16
         self.wq_ok = True
         self._mods = attn_mods
+        self.shared = None
+        if family == "qwen2":
+            sh = self.shared = mlp.shared_expert
+            wgu = getattr(sh, "_ll_gate_up", None)
+            if wgu is None:
+                wgu = torch.cat([sh.gate_proj.weight.detach(), sh.up_proj.weight.detach()], dim=0).contiguous()
+                sh._ll_gate_up, sh._ll_gate_up_key = wgu, _versions(sh.gate_proj.weight, sh.up_proj.weight)
+            self.wgu_s, self.wdown_s, self.Is = wgu, sh.down_proj.weight.detach(), sh.gate_proj.out_features
+            wr = mlp.__dict__.get("_ll_router_gate")
+            if wr is None:
+                wr = torch.cat([mlp.gate.weight.detach(), mlp.shared_expert_gate.weight.detach()], dim=0).contiguous()
+                mlp._ll_router_gate, mlp._ll_router_gate_key = wr, _versions(mlp.gate.weight, mlp.shared_expert_gate.weight)
+            self.router_w = wr
+            self.stream_ok = self.stream_ok and self.Is % 32 == 0
         dev = mlp.gate.weight.device
         key = (self.E, self.top_k, self.H, self.I, str(dev))
         if key not in self._workspaces:
             self._workspaces[key] = _MoeWorkspace(self.lib, dev, self.E, self.top_k, self.H, self.I)
         self.ws = self._workspaces[key]
         self.idx = torch.zeros(MAX_STREAM_ROWS, self.top_k, dtype=torch.int32, device=dev)
-        self.w = torch.zeros(MAX_STREAM_ROWS, self.top_k, dtype=torch.bfloat16, device=dev)
+        self.w = torch.zeros(MAX_STREAM_ROWS, self.top_k, dtype=torch.float32 if self.w_f32 else torch.bfloat16, device=dev)
 
     def _srcs(self):
         return (self.wqkv, self.wo)
@@ -1025,11 +1056,20 @@ class _FusedMoeLayer(_FusedLayer):
         q, k, v, o = self._mods
         return (_versions(q.weight, k.weight, v.weight), _versions(o.weight))
 
+    def _packed64_sources(self):
+        if self.shared is None:
+            return self._srcs(), self._keys64()
+        sh = self.shared
+        return (self._srcs() + (self.wgu_s, self.wdown_s),
+                self._keys64() + (_versions(sh.gate_proj.weight, sh.up_proj.weight), _versions(sh.down_proj.weight)))
+
     def _router_logits(self, h1):
         """[M, E] bf16 = F.linear(rmsnorm(h1), gate.weight): the f32-FMA GEMV up to FMA_GEMV_ROWS rows, the MFMA weight stream beyond, in
         chunks of 16 rows (the router matrix is small and read in place: no packed copy to keep in step)."""
-        M, H, E = h1.shape[0], self.H, self.E
-        wr = self.router.weight
+        M, H = h1.shape[0], self.H
+        # a shared-expert layer: the stacked [E + 1, H] copy -- the output is [M, E + 1], column E the shared gate's logit
+        wr = self.router_w if self.shared is not None else self.router.weight
+        E = wr.shape[0]
         if M <= FMA_GEMV_ROWS or not self.stream_ok:
             return self._gemv(h1, wr, None, self.n2.weight, self.eps2, None, E, H, 0)
         out = torch.empty(M, E, dtype=torch.bfloat16, device=h1.device)
@@ -1041,21 +1081,45 @@ class _FusedMoeLayer(_FusedLayer):
                 _lib.check(rc, "ll_linear_rows16_bf16")
         return out
 
-    def _mlp(self, h1, pq=None):
+    def _shared_rows(self, h1, pre2):
+        """[M, H] bf16 = shared_expert(rmsnorm(h1)) on the dense MLP's kernels: gate|up with the RMSNorm prologue and the SiLU*mul epilogue, down
+        with the plain one -- 1..16 rows on the concatenated copy, 17..64 on the packed copies with ``pre2`` = the pre-norm pair o_proj made."""
+        M, H = h1.shape[0], self.H
+        if M > MAX_ROWS16:
+            xs2, ssq2 = pre2
+            act = _rows64(self.lib, xs2, xs2.stride(0), self.p64[2], None, None, self.Is, 2, row_ssq=ssq2, eps=self.eps2)
+            return _rows64(self.lib, act, act.stride(0), self.p64[3], None, None, H, 0)
+        act = self._gemv(h1, self.wgu_s, None, self.n2.weight, self.eps2, None, self.Is, H, 2)
+        return self._gemv(act, self.wdown_s, None, None, 0.0, None, H, self.Is, 0)
+
+    def _mlp(self, h1, pq=None, pre2=None):
         """Router logits, routing, experts + residual on 1..64 rows of the un-normalised post-attention residual stream h1 [M, H]."""
         M, H = h1.shape[0], self.H
         stream = torch.cuda.current_stream().cuda_stream
         logits = self._router_logits(h1)
-        rc = self.lib.ll_moe_route_bf16(logits.data_ptr(), logits.stride(0), M, self.E, self.top_k, int(self.norm_topk), self.idx.data_ptr(),
-                                        self.w.data_ptr(), self.ws.t.data_ptr(), self.ws.bytes, stream)
+        route = "ll_moe_route_f32" if self.w_f32 else "ll_moe_route_bf16"
+        rc = getattr(self.lib, route)(logits.data_ptr(), logits.stride(0), M, self.E, self.top_k, int(self.norm_topk), self.idx.data_ptr(),
+                                      self.w.data_ptr(), self.ws.t.data_ptr(), self.ws.bytes, stream)
         if rc != 0:
-            _lib.check(rc, "ll_moe_route_bf16")
+            _lib.check(rc, route)
         out = torch.empty(M, H, dtype=torch.bfloat16, device=h1.device)
-        rc = self.lib.ll_moe_experts_bf16(h1.data_ptr(), h1.stride(0), self.n2.weight.data_ptr(), self.eps2, self.idx.data_ptr(), self.w.data_ptr(),
-                                          self.experts.gate_up_proj.data_ptr(), self.experts.down_proj.data_ptr(), h1.data_ptr(), h1.stride(0),
-                                          out.data_ptr(), H, M, self.E, self.top_k, H, self.I, self.ws.t.data_ptr(), self.ws.bytes, stream)
+        if not self.w_f32 and self.shared is None:
+            rc = self.lib.ll_moe_experts_bf16(h1.data_ptr(), h1.stride(0), self.n2.weight.data_ptr(), self.eps2, self.idx.data_ptr(),
+                                              self.w.data_ptr(), self.experts.gate_up_proj.data_ptr(), self.experts.down_proj.data_ptr(),
+                                              h1.data_ptr(), h1.stride(0), out.data_ptr(), H, M, self.E, self.top_k, H, self.I,
+                                              self.ws.t.data_ptr(), self.ws.bytes, stream)
+            if rc != 0:
+                _lib.check(rc, "ll_moe_experts_bf16")
+            return out
+        s = self._shared_rows(h1, pre2) if self.shared is not None else None
+        rc = self.lib.ll_moe_experts_ex_bf16(h1.data_ptr(), h1.stride(0), self.n2.weight.data_ptr(), self.eps2, self.idx.data_ptr(),
+                                             self.w.data_ptr(), int(self.w_f32), self.experts.gate_up_proj.data_ptr(),
+                                             self.experts.down_proj.data_ptr(), h1.data_ptr(), h1.stride(0),
+                                             s.data_ptr() if s is not None else None, s.stride(0) if s is not None else 0,
+                                             logits.data_ptr() + 2 * self.E if s is not None else None, logits.stride(0) if s is not None else 0,
+                                             out.data_ptr(), H, M, self.E, self.top_k, H, self.I, self.ws.t.data_ptr(), self.ws.bytes, stream)
         if rc != 0:
-            _lib.check(rc, "ll_moe_experts_bf16")
+            _lib.check(rc, "ll_moe_experts_ex_bf16")
         return out
 
     def run64(self, h, mask, cache, pe, pre=None, next_norm=None):
@@ -1064,11 +1128,14 @@ class _FusedMoeLayer(_FusedLayer):
         B, H = h.shape[0], self.H
         x = h.view(B, H)
         self.packed64()
-        pqkv, po = self.p64
+        pqkv, po = self.p64[:2]
         xs, ssq = pre if pre is not None else _prenorm64(self.lib, x, self.n1.weight)
         nqkv = self.nq + 2 * self.nkv_dim
         qkv = _rows64(self.lib, xs, xs.stride(0), pqkv, self.bqkv, None, nqkv, 0, row_ssq=ssq, eps=self.eps1)
         att = self._attn(qkv, nqkv, mask, cache, pe, B, h.device)
+        if self.shared is not None:      # the shared expert's gate|up takes the post-attention pre-norm from o_proj's closing launch
+            h1, xs2, ssq2 = _rows64(self.lib, att, att.stride(0), po, self.bo, x, H, 1, next_norm=self.n2.weight)
+            return self._mlp(h1, pre2=(xs2, ssq2)).view(B, 1, H), None
         h1 = _rows64(self.lib, att, att.stride(0), po, self.bo, x, H, 1)
         return self._mlp(h1).view(B, 1, H), None
 
@@ -1110,14 +1177,57 @@ def _is_moe_block(mlp) -> bool:
             or type(mlp).__name__.endswith(("MoeBlock", "MoE")))
 
 
+# block class -> (family, router class, experts class): a family is taken by ALL its parts, never by the block's name alone -- the router class
+# decides the arithmetic of the routing weights (Mixtral: f32, always renormalised; Qwen2-MoE / Qwen3-MoE: bf16, norm_topk_prob)
+MOE_FAMILIES = {"Qwen3MoeSparseMoeBlock": ("qwen3", None, None),
+                "MixtralSparseMoeBlock": ("mixtral", "MixtralTopKRouter", "MixtralExperts"),
+                "Qwen2MoeSparseMoeBlock": ("qwen2", "Qwen2MoeTopKRouter", "Qwen2MoeExperts")}
+
+
+def _moe_family(mlp) -> Optional[str]:
+    """"qwen3" | "mixtral" | "qwen2" for a block of a fused family, None for any other."""
+    family, router, experts = MOE_FAMILIES.get(type(mlp).__name__, (None, None, None))
+    if family is None or (router is not None and (type(getattr(mlp, "gate", None)).__name__ != router
+                                                  or type(getattr(mlp, "experts", None)).__name__ != experts)):
+        return None
+    return family
+
+
+def _shared_expert_declined(mlp, hidden: int) -> Optional[str]:
+    """The shared expert of a Qwen2MoeSparseMoeBlock: a dense gated MLP of three plain bias-free nn.Linear with SiLU, and a one-row gate."""
+    sh, sg = getattr(mlp, "shared_expert", None), getattr(mlp, "shared_expert_gate", None)
+    lin = [getattr(sh, a, None) for a in ("gate_proj", "up_proj", "down_proj")]
+    if not all(type(m) is nn.Linear for m in lin) or type(sg) is not nn.Linear:
+        return "shared expert whose projections are not plain nn.Linear"
+    if any(m.bias is not None for m in lin) or sg.bias is not None:
+        return "shared expert bias"
+    if not _is_silu(getattr(sh, "act_fn", None)):
+        return "shared expert activation is not SiLU"
+    Is = lin[0].out_features
+    if (tuple(lin[0].weight.shape) != (Is, hidden) or tuple(lin[1].weight.shape) != (Is, hidden) or tuple(lin[2].weight.shape) != (hidden, Is)
+            or tuple(sg.weight.shape) != (1, hidden)):
+        return "shared expert is not gate_proj / up_proj [I_s, H], down_proj [H, I_s] with a shared_expert_gate [1, H]"
+    if Is % 8 != 0:
+        return "shared_expert_intermediate_size is not a multiple of 8"
+    if Is > MOE_MAX_INTERMEDIATE:
+        return f"shared_expert_intermediate_size above {MOE_MAX_INTERMEDIATE}"
+    return None
+
+
 def _moe_block_declined(mlp, hidden: int) -> Optional[str]:
-    """The structural part of ``decoder_layer_declined`` for a sparse-MoE block: only the Qwen3-MoE layout is fused (softmax over all experts,
-    top-k, optional renormalisation, SiLU experts stored as [E, 2I, H] / [E, H, I], no shared expert, no biases).  Other router families
-    (Mixtral, Qwen2-MoE with a shared expert, DeepSeek) have different semantics and are named, not guessed at."""
+    """The structural part of ``decoder_layer_declined`` for a sparse-MoE block.  Fused: the Qwen3-MoE layout (softmax over all experts, top-k,
+    optional renormalisation, SiLU experts stored as [E, 2I, H] / [E, H, I], no shared expert, no biases), the Mixtral layout (the same with
+    f32 routing weights, always renormalised) and the Qwen2-MoE layout (the Qwen3 routing plus a sigmoid-gated shared expert).  Other router
+    families (DeepSeek, GPT-OSS) have different semantics and are named, not guessed at."""
     kind = type(mlp).__name__
-    if kind != "Qwen3MoeSparseMoeBlock":
+    family = _moe_family(mlp)
+    if family is None:
         return f"MoE block of an unsupported kind ({kind})"
-    if any(getattr(mlp, a, None) is not None for a in ("shared_expert", "shared_experts", "shared_expert_gate")):
+    if family == "qwen2":
+        why = _shared_expert_declined(mlp, hidden)
+        if why is not None:
+            return why
+    elif any(getattr(mlp, a, None) is not None for a in ("shared_expert", "shared_experts", "shared_expert_gate")):
         return "MoE block of an unsupported kind (shared expert)"
     experts, gate = getattr(mlp, "experts", None), getattr(mlp, "gate", None)
     wgu, wd, wr = getattr(experts, "gate_up_proj", None), getattr(experts, "down_proj", None), getattr(gate, "weight", None)
@@ -1126,7 +1236,7 @@ def _moe_block_declined(mlp, hidden: int) -> Optional[str]:
     E, H, I = wd.shape
     if tuple(wgu.shape) != (E, 2 * I, H) or tuple(wr.shape) != (E, H) or H != hidden:
         return "MoE block of an unsupported kind (experts are not gate_up_proj [E, 2I, H] / down_proj [E, H, I] parameters with a gate.weight [E, H])"
-    if not hasattr(gate, "top_k") or not hasattr(gate, "norm_topk_prob"):
+    if not hasattr(gate, "top_k") or (family != "mixtral" and not hasattr(gate, "norm_topk_prob")):      # (Mixtral's router always renormalises)
         return "MoE router without top_k / norm_topk_prob"
     if any(getattr(m, a, None) is not None for m in (experts, gate) for a in ("bias", "gate_up_proj_bias", "down_proj_bias")):
         return "MoE expert bias"
@@ -1146,10 +1256,15 @@ def _moe_block_declined(mlp, hidden: int) -> Optional[str]:
 def attn_window(att):
     """The sliding window of an HF attention module, None for full attention: its ``sliding_window`` attribute where the class has one (Qwen2 /
     Qwen3 / Ministral: None on the full layers of a mixed model), else its config's -- MistralAttention keeps none and hands
-    ``config.sliding_window`` to the attention call."""
+    ``config.sliding_window`` to the attention call.  Qwen2MoeAttention sets the attribute on its sliding layers only and its config holds
+    ``sliding_window = 0`` when windows are off: a layer without the attribute that ``layer_types`` names "full_attention" has no window."""
     if hasattr(att, "sliding_window"):
         return att.sliding_window
-    return getattr(getattr(att, "config", None), "sliding_window", None)
+    cfg = getattr(att, "config", None)
+    types, idx = getattr(cfg, "layer_types", None), getattr(att, "layer_idx", None)
+    if types is not None and isinstance(idx, int) and 0 <= idx < len(types) and types[idx] != "sliding_attention":
+        return None
+    return getattr(cfg, "sliding_window", None)
 
 
 def _config_window(att):
@@ -1209,6 +1324,9 @@ def decoder_layer_declined(layer: nn.Module) -> Optional[str]:
         return MOE_RESIDUAL_MULTIPLIER_DECLINED
     norms = [m for m in (getattr(att, "q_norm", None), getattr(att, "k_norm", None)) if m is not None]
     extra = [m.weight for m in norms] + ([mlp.experts.gate_up_proj, mlp.experts.down_proj, mlp.gate.weight] if moe else [])
+    if moe and _moe_family(mlp) == "qwen2":
+        sh = mlp.shared_expert
+        extra += [sh.gate_proj.weight, sh.up_proj.weight, sh.down_proj.weight, mlp.shared_expert_gate.weight]
     if att.q_proj.weight.dtype != torch.bfloat16 or any(t.dtype != torch.bfloat16 for t in extra):
         return "weights are not bf16"
     if not att.q_proj.weight.is_cuda or not all(t.is_cuda for t in extra):
@@ -1250,6 +1368,8 @@ def restore_decoder_layers(model: nn.Module) -> None:
             for sub in layer.modules():       # the layer's concatenated gate|up copy goes with it (rebuilt on the next install)
                 sub.__dict__.pop("_ll_gate_up", None)
                 sub.__dict__.pop("_ll_gate_up_key", None)
+                sub.__dict__.pop("_ll_router_gate", None)
+                sub.__dict__.pop("_ll_router_gate_key", None)
 
 
 # ------------------------------------------------------------------------------------------ whole decode step of the base model
@@ -1558,6 +1678,8 @@ def accelerate_llm(model: nn.Module, linears: bool = True, fuse: bool = True, la
         q["packed_routes"] = {m: (sorted(WQ_ROUTES.get((bits, m), ())) if FMA_GEMV_ROWS == 2 else []) for m in WQ_MATRICES}
         if any(_is_moe_block(getattr(l, "mlp", None)) for l in (getattr(base, "layers", None) or [])):
             q["experts"] = "bf16"       # expert and router weights are neither rounded nor packed: only the attention Linears of a MoE layer are
+        if any(getattr(getattr(l, "mlp", None), "shared_expert", None) is not None for l in (getattr(base, "layers", None) or [])):
+            q["shared_expert"] = "bf16"     # a shared expert's Linears are rounded, not packed: they run the bf16 kernels on the dequantised weights
         if any(st is not None and st.rscale is not None and st.wq_bits is not None for st in fused):
             q["bf16_reason"] = WQ_RESIDUAL_MULTIPLIER_REASON
     return info

@@ -123,6 +123,12 @@ def layer_linears(model: nn.Module):
             mod = getattr(getattr(layer, parent, None), name, None)
             if isinstance(mod, nn.Linear):
                 yield f"layers.{i}.{parent}.{name}", mod
+        # a shared-expert MoE block (Qwen2-MoE): the shared expert's three Linears are rounded like any other; they keep running the bf16 kernels
+        shared = getattr(getattr(layer, "mlp", None), "shared_expert", None)
+        for name in ("gate_proj", "up_proj", "down_proj"):
+            mod = getattr(shared, name, None)
+            if isinstance(mod, nn.Linear):
+                yield f"layers.{i}.mlp.shared_expert.{name}", mod
 
 
 def quantize_llm(model: nn.Module, bits: int) -> dict:

@@ -1,15 +1,17 @@
-"""Decode token of the graphed decoder on a sparse-MoE model (Qwen3-MoE layout) at Qwen3-30B-A3B widths (random bf16 weights, the router drawn
-wider than HF's init so that the routing is not a near-tie everywhere):
-python tools/decode_moe_time.py [--out profiles/decode_moe_time.txt] [--new N] [--rows 1,16,64] [--arch qwen3-30b-a3b] [--layers L]
-(--arch: any Qwen3Moe entry of e2e.LLM_CONFIGS, e.g. tiny-qwen3-moe for a dry run; --layers: fewer decoder layers, stated in the output).
+"""Decode token of the graphed decoder on a sparse-MoE model at Qwen3-30B-A3B widths, or with --model at Mixtral-8x7B / Qwen1.5-MoE-A2.7B
+widths (random bf16 weights, the router drawn wider than HF's init so that the routing is not a near-tie everywhere):
+python tools/decode_moe_time.py [--out profiles/decode_moe_time.txt] [--new N] [--rows 1,16,64] [--model qwen3-30b-a3b] [--layers L] [--append]
+(--model, or --arch: any sparse-MoE entry of e2e.LLM_CONFIGS -- qwen3-30b-a3b, mixtral-8x7b, qwen1.5-moe-a2.7b, or a tiny one for a dry run;
+--layers: fewer decoder layers, stated in the output; --append: add to --out instead of replacing it).
 Two models with the same weights live in one process:
-  (i)   the fused stack: MoE layers as eight launches (ll_moe_route_bf16 / ll_moe_experts_bf16), one-launch prologue;
+  (i)   the fused stack: MoE layers as eight launches (ll_moe_route_bf16 / ll_moe_experts_bf16; Mixtral: ll_moe_route_f32 /
+        ll_moe_experts_ex_bf16; Qwen2-MoE: ten, with the shared expert's two Linears), one-launch prologue;
   (ii)  accelerate_llm(layers=False): what such a model ran before its layers were accepted -- fused Linears, RMSNorm, rotary and attention
         kernels op by op under HF's layer code, HF's experts code (config._experts_implementation is recorded) per layer.
 Per row count both see the same prompts; the token time is (generate(1 + n) - generate(1)) / n, median of 3, greedy, after a 128-token prompt,
 the cases taken alternately over three repeats after a warm-up of both.  For (i) the file also gives the bytes of weights one decode step
 touches -- the distinct experts per layer counted from the routing (`idx`) of the last step, read after the run -- and the TB/s that implies.
-Then ll_moe_experts_bf16 alone (HIP events, cycling through the layers' expert matrices so that no launch finds its weights in the Infinity
+Then the experts call alone (ll_moe_experts_bf16, for Mixtral ll_moe_experts_ex_bf16 with f32 weights; without the shared expert; HIP events, cycling through the layers' expert matrices so that no launch finds its weights in the Infinity
 Cache) at 1 / 16 / 64 rows with a routing drawn uniformly and with all rows on the same top_k experts."""
 import os
 import sys
@@ -26,11 +28,14 @@ argv = sys.argv[1:]
 n = int(argv[argv.index("--new") + 1]) if "--new" in argv else 128
 out_path = argv[argv.index("--out") + 1] if "--out" in argv else os.path.join("profiles", "decode_moe_time.txt")
 rows = tuple(int(x) for x in argv[argv.index("--rows") + 1].split(",")) if "--rows" in argv else (1, 16, 64)
-arch = argv[argv.index("--arch") + 1] if "--arch" in argv else "qwen3-30b-a3b"
+arch = next((argv[argv.index(f) + 1] for f in ("--model", "--arch") if f in argv), "qwen3-30b-a3b")
 over = {"num_hidden_layers": int(argv[argv.index("--layers") + 1])} if "--layers" in argv else {}
 REPEATS = 3
 WINDOW_MS = 100.0       # timed window of the kernel-alone figures
 lines = []
+if "--append" in argv and os.path.exists(out_path):       # keep what an earlier run (another --model) wrote
+    with open(out_path) as fh:
+        lines = fh.read().splitlines() + [""]
 
 
 def say(s):
@@ -80,6 +85,8 @@ def step_bytes(llm, B):
             k = int(st.idx[:B].flatten().unique().numel())
             distinct.append(k)
             total += st.router.weight.numel() + k * 3 * st.I * st.H
+            if st.shared is not None:       # the shared expert's three matrices and its gate row, read at every step
+                total += st.wgu_s.numel() + st.wdown_s.numel() + st.H
         else:
             total += st.wgu.numel() + st.wdown.numel()
     total += llm.lm_head.weight.numel() + llm.model.norm.weight.numel() + B * llm.config.hidden_size
@@ -102,14 +109,16 @@ def experts_alone(llm):
             if kind == "same experts":
                 logits = logits[:1].repeat(M, 1)
             logits = logits.to(torch.bfloat16).cuda()
-            _lib.check(lib.ll_moe_route_bf16(logits.data_ptr(), E, M, E, k, 1, st0.idx.data_ptr(), st0.w.data_ptr(), st0.ws.t.data_ptr(), st0.ws.bytes,
-                                             stream), "ll_moe_route_bf16")
+            route = lib.ll_moe_route_f32 if st0.w_f32 else lib.ll_moe_route_bf16
+            _lib.check(route(logits.data_ptr(), E, M, E, k, 1, st0.idx.data_ptr(), st0.w.data_ptr(), st0.ws.t.data_ptr(), st0.ws.bytes, stream),
+                       "ll_moe_route")
             distinct = int(st0.idx[:M].flatten().unique().numel())
 
             def run(st):
-                _lib.check(lib.ll_moe_experts_bf16(x.data_ptr(), H, st.n2.weight.data_ptr(), st.eps2, st0.idx.data_ptr(), st0.w.data_ptr(),
-                                                   st.experts.gate_up_proj.data_ptr(), st.experts.down_proj.data_ptr(), x.data_ptr(), H,
-                                                   out.data_ptr(), H, M, E, k, H, I, st0.ws.t.data_ptr(), st0.ws.bytes, stream), "ll_moe_experts_bf16")
+                _lib.check(lib.ll_moe_experts_ex_bf16(x.data_ptr(), H, st.n2.weight.data_ptr(), st.eps2, st0.idx.data_ptr(), st0.w.data_ptr(),
+                                                      int(st0.w_f32), st.experts.gate_up_proj.data_ptr(), st.experts.down_proj.data_ptr(),
+                                                      x.data_ptr(), H, None, 0, None, 0, out.data_ptr(), H, M, E, k, H, I, st0.ws.t.data_ptr(),
+                                                      st0.ws.bytes, stream), "ll_moe_experts_ex_bf16")
             def window(inner):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 torch.cuda.synchronize()
@@ -125,13 +134,19 @@ def experts_alone(llm):
             reps = [1000 * window(inner) / (inner * len(sts)) for _ in range(REPEATS)]
             med = sorted(reps)[1]
             nbytes = 2 * distinct * 3 * I * H
-            say(f"ll_moe_experts_bf16 alone, rows {M:2d}, {kind}: {distinct} distinct experts ({nbytes / 1e6:.1f} MB of expert weights), median "
+            label = ("ll_moe_experts_ex_bf16 (f32 weights)" if st0.w_f32 else
+                     "ll_moe_experts_ex_bf16 (no option: it forwards to ll_moe_experts_bf16)")
+            say(f"{label} alone, rows {M:2d}, {kind}: {distinct} distinct experts ({nbytes / 1e6:.1f} MB of expert weights), median "
                 f"{med:.1f} us (min {min(reps):.1f} - max {max(reps):.1f}) over {len(sts)} layers' matrices in turn, {inner * len(sts)} calls per window = "
                 f"{nbytes / med / 1e6:.2f} TB/s")
 
 
+# the entry points a fused MoE layer of this model's family calls (llm_accel._FusedMoeLayer._mlp)
+ENTRIES = {"Mixtral": "ll_moe_route_f32 / ll_moe_experts_ex_bf16 with f32 weights",
+           "Qwen2Moe": "ll_moe_route_bf16 / ll_moe_experts_ex_bf16 with the shared expert"}.get(e2e.LLM_CONFIGS[arch]["cls"],
+                                                                                             "ll_moe_route_bf16 / ll_moe_experts_bf16")
 say(f"# decode token at {arch} widths{' with ' + str(over['num_hidden_layers']) + ' decoder layers' if over else ''}: sparse-MoE layers fused "
-    f"(ll_moe_route_bf16 / ll_moe_experts_bf16) against the same model with accelerate_llm(layers=False)")
+    f"({ENTRIES}) against the same model with accelerate_llm(layers=False)")
 say(f"# n = {n} tokens after a 128-token prompt, greedy, median of 3 per figure, {REPEATS} alternated repeats")
 CASES = (("(i) fused", {}), ("(ii) layers=False", dict(layers=False)))
 models, llms = {}, {}
